@@ -1,8 +1,21 @@
 """bench.py — batched 64-bit range-proof verification on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--n 64]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--n 64] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set-up (generators, prefix tables, the
+resident batches), warm-up, the K timed steps, --dump-outputs if given, the JSON line (`value`,
+`ms_per_step`, the live roofline of the timed region).  Every other leg listed below (CPU baselines,
+configs[0], the self-check, MSM, IPA, prover, prefix widths, repeats, H2D, shard, host API) runs only
+with --full, where the --no-* switches still turn single legs off; without --full those fields are null.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path left in its callers' buffers:
+DIR/verdicts.npy (float32, batches x B: the verdict bytes of the resident batches as the timed steps
+wrote them, pipelines drained) and DIR/P_last.npy (float64, B x 32: the IPA point P of the last timed
+step's batch as 32-bit halves of its u64 limbs, low half first, from one more untimed pass of that
+batch through the same pipeline, whose verdicts must equal the timed ones).  Inputs are seeded, so two
+builds run with the same arguments can be compared file for file.
 
 --gpus N is N ranks: without a launcher, bench.py starts torch.distributed.run on itself as a
 child process (before touching the GPU) and exits with its status; under a launcher WORLD_SIZE
@@ -14,7 +27,7 @@ One step = cuda_range_proof_verify semantics (crv:82) over one batch of B = 1024
 batches (weak scaling, no data-path collective: proofs are independent).  K steps are timed
 between barrier + synchronize on both sides; the max over ranks is the step time.
 
-Extra fields on the JSON line:
+Extra fields on the JSON line (all but roofline need --full):
   roofline     SURVEY 8(d) algorithmic bytes per step / ms_per_step vs HBM peak (the path is
                VALU-integer bound; see DESIGN.md), PMC traffic per launch; valu_roofline beside it;
   cpu_baseline the CPU restatement (oracle/, test infrastructure) on a bounded sample, 1 thread;
@@ -109,7 +122,18 @@ def parse():
     ap.add_argument("--no-repeats", action="store_true", help="skip the 5 repeated timed regions (repeats)")
     ap.add_argument("--rehearse", action="store_true",
                     help="exercise the N>1 path on one GPU (all ranks on cuda:0, gloo collectives); not a measurement")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (CPU baselines, configs[0], self-check, MSM, IPA, "
+                         "prover, prefix widths, repeats, H2D, shard, host API); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the timed path's outputs to DIR/verdicts.npy and "
+                         "DIR/P_last.npy (see the module docstring)")
+    args = ap.parse_args()
+    if not args.full:   # a plain run: the headline alone
+        for leg in ("cpu", "check", "msm", "repeats", "h2d", "shard", "ipa", "host", "prove"):
+            setattr(args, "no_" + leg, True)
+        args.table_legs = ""
+    return args
 
 
 TASK_B = GE_B + FE_B + GE_B   # one scalar-mult task: point + scalar in, term out
@@ -794,6 +818,40 @@ def headline_check(B, n, pipes, streams, batch, Gd, Hd, hd, sample):
     return res
 
 
+def dump_outputs(args, dev, pipes, streams, batches, oks, gens4):
+    """--dump-outputs: the timed path's outputs after its last step, pipelines drained (the caller
+    flushed them).  verdicts.npy: the verdict buffers the timed steps wrote (pipeline mode: one row
+    per resident batch; oneshot mode: one row per stream slot).  P_last.npy: the last timed step's
+    batch once more through the same pipeline (oneshot: the same call) with P_out set, outside the
+    timed region; its verdicts must equal the row the timed steps wrote.  Seeded inputs: the same
+    arguments give the same files."""
+    import torch
+    import cudabulletproof_amd as bp
+    B, last = args.batch, args.steps - 1
+    ok2 = torch.zeros(B, dtype=torch.uint8, device=dev)
+    P = torch.zeros(B, 16, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)   # the zero fills are on torch's stream, the verify is not
+    batch = batches[last % len(batches)]
+    if pipes:
+        rows, row = oks[:len(batches)], last % len(batches)
+        pl = pipes[last % len(pipes)]
+        pl.push(batch, ok2, P_out=P)
+        pl.flush()
+    else:
+        ns = max(1, args.streams, args.pipes)
+        rows, row = oks[:ns], last % ns
+        bp.batch_range_proof_verify(batch, *gens4, ok2, P_out=P, stream=streams[last % ns])
+    torch.cuda.synchronize(dev)
+    if not torch.equal(ok2, rows[row]):
+        raise SystemExit("bench.py: --dump-outputs: the last step's batch verified again gave other verdicts "
+                         "than the timed step wrote")
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "verdicts.npy"),
+            torch.stack(list(rows)).cpu().numpy().astype(np.float32))
+    limbs = np.ascontiguousarray(P.cpu().numpy()).view(np.uint32)   # (B, 32): low half of each limb first
+    np.save(os.path.join(args.dump_outputs, "P_last.npy"), limbs.astype(np.float64))
+
+
 def h2d_leg(args, dev, pipes, batches, steps, want_oks=None):
     """The headline with the per-batch proof H2D inside the timed region (SURVEY §8(d) timing rule):
     every step copies its batch (B proofs in the flat wire format, ≈2.3 KB each) from pinned host
@@ -1451,6 +1509,8 @@ def main():
     for pp in pipes:
         pp.flush()
     torch.cuda.synchronize(dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, dev, pipes, streams, batches, oks, (Gd, Hd, gd, hd))
     prefix_legs = None
     if pipes and args.table_legs.strip():   # the same workload at other table widths, e.g. none (K = 0)
         ref_oks = [o.clone() for o in oks[:nb]]
@@ -1516,7 +1576,7 @@ def main():
             "metric": "64-bit range-proof verifies/sec (batched)", "value": value, "unit": "verifies/s",
             "n_gpus": world, "world_size": world_seen, "distinct_devices": len({r["pci"] for r in ranks}),
             "backend": dist.get_backend() if world > 1 else None, "ranks": ranks,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
             "data": ("synthetic: real 64-bit range proofs of random values made by the GPU prover "
                      "(generate_range_proof semantics, seeded randomness); generators per "

@@ -52,6 +52,20 @@ def test_shard_push_batch():
     assert bench.shard_push_batch(a, 8192, 2) == 512
 
 
+def test_plain_run_is_the_headline_alone(monkeypatch):
+    # without --full every leg beside the headline is off; with it the --no-* switches decide
+    legs = ("cpu", "check", "msm", "repeats", "h2d", "shard", "ipa", "host", "prove")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3",
+                                      "--dump-outputs", "d"])
+    a = bench.parse()
+    assert not a.full and a.steps == 7 and a.warmup == 3 and a.dump_outputs == "d"
+    assert all(getattr(a, "no_" + k) for k in legs) and a.table_legs == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-ipa"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs is None and a.no_ipa and a.table_legs == "0,16"
+    assert not any(getattr(a, "no_" + k) for k in legs if k != "ipa")
+
+
 def test_cpu_share(monkeypatch):
     monkeypatch.setenv("OMP_NUM_THREADS", "3")
     nproc, aff, used = bench.cpu_share()
@@ -177,7 +191,7 @@ def test_launcher_parent_is_hip_free_and_hands_cpu_legs_to_rank0():
     and it runs the CPU baseline + configs[0] legs itself, so the N-rank line carries them
     (BENCH_LAUNCH_DRYRUN=1: the parent prints the hand-over instead of spawning)."""
     import json
-    p = _run_bench(["--gpus", "2", "--rehearse", "--cpu-seconds", "0.3", "--cpu-procs", "1"],
+    p = _run_bench(["--full", "--gpus", "2", "--rehearse", "--cpu-seconds", "0.3", "--cpu-procs", "1"],
                    {"BENCH_LAUNCH_DRYRUN": "1"}, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     legs = json.loads(p.stdout.strip().splitlines()[-1])

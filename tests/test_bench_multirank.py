@@ -11,7 +11,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "2", "--warmup", "1", "--batch", "128", "--msm-log2", "12", "--prefix-bits", "12",
+SMALL = ["--full", "--steps", "2", "--warmup", "1", "--batch", "128", "--msm-log2", "12", "--prefix-bits", "12",
          "--shard-total", "3000", "--no-host", "--no-cpu", "--no-ipa", "--no-prove"]
 
 
@@ -85,6 +85,38 @@ def test_bench_ranks_rehearsal_matches_one_rank(one_rank_line, N):
     if N in (4, 8):   # the N-rank line carries the CPU baseline (parent or rank 0 timed it)
         assert l2["cpu_baseline"] is not None and l2["cpu_baseline"]["value"] > 0
         assert l2["configs0"] is not None
+
+
+@pytest.mark.gpu
+def test_plain_run_is_headline_alone_and_dumps_its_outputs(one_rank_line, tmp_path):
+    """Without --full the line carries the headline and none of the other legs, and --dump-outputs
+    writes the timed path's verdicts (the bytes the --full run's rank digest covers, same seeds) and
+    the last step's IPA points as float arrays."""
+    import hashlib
+    import numpy as np
+    out = str(tmp_path / "dump")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--batch", "128", "--prefix-bits", "12", "--dump-outputs", out], capture_output=True,
+                       text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    l, l1 = _line(p.stdout), one_rank_line
+    assert l["full"] is False and l1["full"] is True
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert l[k] == l1[k]
+    assert l["steps"] == 2 and l["ms_per_step"] > 0 and l["value"] > 0
+    assert abs(l["value"] * l["ms_per_step"] * 1e-3 / 128 - 1) < 1e-9   # one step = one batch of 128
+    for k in ("cpu_baseline", "configs0", "verify_check", "msm", "ipa", "prove", "prefix_legs", "repeats", "with_h2d",
+              "sharded_2p16", "host_api"):
+        assert l[k] is None, k
+    assert l["roofline"]["kernel"] and l1["msm"] is not None and l1["repeats"] is not None
+    v = np.load(os.path.join(out, "verdicts.npy"))
+    assert v.dtype == np.float32 and v.shape == (4, 128) and set(np.unique(v)) <= {0.0, 1.0}
+    digest = hashlib.sha256(v.astype(np.uint8).tobytes()).hexdigest()[:16]
+    assert digest == l["ranks"][0]["verdicts_sha256"] == l1["ranks"][0]["verdicts_sha256"]
+    assert int(v.sum()) == l["ranks"][0]["passes"]
+    P = np.load(os.path.join(out, "P_last.npy"))
+    assert P.dtype == np.float64 and P.shape == (128, 32)
+    assert np.array_equal(P, np.floor(P)) and P.min() >= 0 and P.max() < 2.0 ** 32 and np.count_nonzero(P) > 128 * 16
 
 
 @pytest.mark.gpu

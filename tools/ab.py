@@ -5,7 +5,7 @@ library swapped in as the product library for that run; the original is restored
 plain bench.py arguments.  Configurations run alternately, `--reps` times each, one bench.py child
 process per run under its own time limit; the first failing run ends the A/B (no retries).
 
-  python tools/ab.py --tag r05k --reps 2 --base "--no-cpu --no-ipa --no-msm --no-shard --no-host" \
+  python tools/ab.py --tag r05k --reps 2 --base "--full --no-cpu --no-ipa --no-msm --no-shard --no-host" \
       --cfg "K16: --prefix-bits 16" --cfg "K23: --prefix-bits 23" \
       --pick value --pick repeats.median --pick prove.value
 

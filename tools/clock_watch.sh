@@ -8,7 +8,7 @@ TAG=${1:-cw}
 STEPS=${2:-2000}
 OUT=gpurun_out/clock_$TAG
 mkdir -p "$OUT"
-timeout -k 10 400 python3 bench.py --steps "$STEPS" --warmup 5 --no-cpu --no-ipa --no-msm --no-prove --no-shard \
+timeout -k 10 400 python3 bench.py --full --steps "$STEPS" --warmup 5 --no-cpu --no-ipa --no-msm --no-prove --no-shard \
     --no-host --no-h2d --no-check --table-legs= > "$OUT/bench.json" 2> "$OUT/bench.err" &
 BPID=$!
 while kill -0 "$BPID" 2> /dev/null; do

@@ -8,7 +8,7 @@ TAG=${1:-r01}
 OUT=gpurun_out/prof_${TAG}_prove
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-RUN="python3 bench.py --steps 2 --warmup 1 --no-cpu --no-ipa --no-msm --no-shard --no-host --no-check --no-h2d --no-repeats --table-legs= --prove-steps 2"
+RUN="python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-ipa --no-msm --no-shard --no-host --no-check --no-h2d --no-repeats --table-legs= --prove-steps 2"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- $RUN > "$OUT/bench_trace.json" 2> "$OUT/trace.log"
 timeout -k 10 300 rocprofv3 --pmc VALUBusy VALUUtilization --kernel-trace --output-format csv -d "$OUT/pmc_busy" -o run -- $RUN > /dev/null 2> "$OUT/busy.log"
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OUT/pmc_valu" -o run -- $RUN > /dev/null 2> "$OUT/valu.log"
