@@ -24,7 +24,7 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libcudabulletproof_hip.so")
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["bp_terms1.hip", "bp_terms2.hip", "bp_terms4.hip", "bp_terms16.hip", "bp_kernels.hip", "bp_prove.hip",
-           "bp_pippenger.hip", "bp_capi.hip"]
+           "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_capi.hip"]
 
 _lib = None
 
@@ -99,6 +99,14 @@ class ProofOutC(ctypes.Structure):   # hipbp_proof_out
     _fields_ = [(k, _c) for k in ("V", "A", "S", "T1", "T2", "taux", "mu", "t", "c", "x", "a", "b", "L", "R", "valid")]
 
 
+class ProveIpaInputC(ctypes.Structure):   # hipbp_ipa_prove_input
+    _fields_ = [("count", _sz), ("n", _sz)] + [(k, _c) for k in ("a", "b", "c", "transcript")]
+
+
+class IpaProofOutC(ctypes.Structure):   # hipbp_ipa_proof_out
+    _fields_ = [(k, _c) for k in ("a", "b", "c", "x", "c_final", "L", "R")]
+
+
 assert ctypes.sizeof(InnerProductProof) == 144 and ctypes.sizeof(RangeProofC) == 880
 
 EXPORTS = [
@@ -117,6 +125,7 @@ EXPORTS = [
     "hipbp_pipeline_push", "hipbp_pipeline_flush", "hipbp_pipeline_depth", "hipbp_pipeline_destroy",
     "hipbp_pipeline_defer_msm",
     "hipbp_release_stream_workspaces",
+    "hipbp_batch_inner_product_prove", "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host",
 ]
 
 
@@ -143,7 +152,8 @@ def lib():
                   "hipbp_msm_pippenger", "hipbp_msm_pippenger_batch", "hipbp_msm_pippenger_windows",
                   "hipbp_msm_pippenger_horner", "hipbp_msm_batch", "hipbp_msm_batch_gens", "hipbp_point_tree",
                   "hipbp_field_op", "hipbp_sha_probe", "hipbp_sync", "hipbp_device_count",
-                  "hipbp_release_stream_workspaces"):
+                  "hipbp_release_stream_workspaces", "hipbp_batch_inner_product_prove",
+                  "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host"):
             getattr(L, f).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -472,6 +482,84 @@ def batch_generate_range_proof(n, v, gamma, sL, sR, rnd, G, H, g, h, stream=None
                                                     _stream_ptr(stream)))
     out["_keep"] = ins
     return out
+
+
+def batch_inner_product_prove(n, a, b, c, G, H, Q, transcript=None, stream=None, gens=None):
+    """inner_product_prove (bulletproof_vectors.cu:277) over a batch, on the GPU, for any power-of-two
+    n up to 65536 (hipbp_batch_inner_product_prove).
+
+    a, b (B,n,4); c (B,4) the claimed inner products; transcript (B,4) the 32 initial transcript bytes
+    as LE limbs (None: zeros); G, H (n,16), Q (16,): int64 CUDA tensors of the u64 limbs.  With
+    gens= a Generators set, its G, H and prefix tables are used and Q is its h (G, H, Q are not
+    read); the bits are the same.  Returns a dict of CUDA tensors: a, b (B,1,4), c, c_final, x (B,4),
+    L, R (B,log2 n,16); c is the claimed value as given, c_final = add(0, mul(a, b)) of the final a, b,
+    the value with which the reference's verifier accepts.  ipa_proof_batch() makes it verifiable."""
+    import contextlib
+
+    import torch
+    B = int(a.shape[0])
+    Lr = int(n).bit_length() - 1
+    dev = a.device
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+        out = dict(a=z(B, 1, 4), b=z(B, 1, 4), c=z(B, 4), x=z(B, 4), c_final=z(B, 4), L=z(B, max(Lr, 0), 16),
+                   R=z(B, max(Lr, 0), 16))
+    ins = [t.contiguous() for t in (a, b, c)] + [transcript.contiguous() if transcript is not None else None]
+    if ins[0].numel() != B * int(n) * 4 or ins[1].numel() != B * int(n) * 4 or ins[2].numel() != B * 4:
+        raise BulletproofError("batch_inner_product_prove: a, b must be (B, n, 4) and c (B, 4)")
+    ic = ProveIpaInputC(B, int(n), *[t.data_ptr() if t is not None else None for t in ins])
+    oc = IpaProofOutC(*[out[k].data_ptr() if out[k].numel() else None for k in ("a", "b", "c", "x", "c_final", "L", "R")])
+    if gens is not None:
+        _chk(lib().hipbp_batch_inner_product_prove_gens(ctypes.byref(ic), _c(gens.h), ctypes.byref(oc),
+                                                        _stream_ptr(stream)))
+    else:
+        _chk(lib().hipbp_batch_inner_product_prove(ctypes.byref(ic), _c(G.data_ptr()), _c(H.data_ptr()),
+                                                   _c(Q.data_ptr()), ctypes.byref(oc), _stream_ptr(stream)))
+    out["_keep"] = ins
+    return out
+
+
+def ipa_proof_batch(n, proof, c="c_final"):
+    """A batch_inner_product_prove result as a RangeProofBatch for batch_inner_product_verify (zero
+    V, A, S, T1, T2, t, which the inner-product check does not read).  c: "c_final" (the value the
+    reference's verifier accepts with) or "c" (the claimed value as given)."""
+    import torch
+    if c not in ("c", "c_final"):
+        raise ValueError("c must be 'c' or 'c_final'")
+    B, dev = int(proof["a"].shape[0]), proof["a"].device
+    zp = torch.zeros(B, 16, dtype=torch.int64, device=dev)
+    return RangeProofBatch(n, V=zp, A=zp, S=zp, T1=zp, T2=zp, t=torch.zeros(B, 4, dtype=torch.int64, device=dev),
+                           a=proof["a"], b=proof["b"], c=proof[c], x=proof["x"], L=proof["L"], R=proof["R"])
+
+
+def inner_product_prove(a, b, G, H, Q, c, transcript=None):
+    """inner_product_prove on host arrays through hipbp_inner_product_prove_host (the reference's own
+    structs): a, b (n,4), G, H (n,16), Q (16,), c (4,) uint64; transcript 32 bytes (None: zeros).
+    Returns dict(a, b (1,4), c, x (4,), L, R (log2 n,16)), or None where the reference's function
+    returns early (length mismatch, n no power of two)."""
+    require_gpu()
+    a, b, G, H = _u64(a, 4), _u64(b, 4), _u64(G, 16), _u64(H, 16)
+    Q, c = _u64(Q, 16), _u64(c, 4)
+    tr = np.zeros(32, np.uint8) if transcript is None else np.ascontiguousarray(transcript, np.uint8)
+    pr = InnerProductProof()
+    av, bv = FieldVector(_p(a).value, len(a)), FieldVector(_p(b).value, len(b))
+    gv, hv = PointVector(_p(G).value, len(G)), PointVector(_p(H).value, len(H))
+    rc = lib().hipbp_inner_product_prove_host(ctypes.byref(pr), ctypes.byref(av), ctypes.byref(bv), ctypes.byref(gv),
+                                              ctypes.byref(hv), _p(Q), _p(c), _p(tr))
+    if rc != 0:
+        if not pr.a.elements and rc == 1:
+            return None
+        _chk(rc)
+    libc = ctypes.CDLL(None)
+    libc.free.argtypes = [ctypes.c_void_p]
+
+    def take(vec, words):
+        out = np.ctypeslib.as_array(ctypes.cast(vec.elements, ctypes.POINTER(ctypes.c_uint64)),
+                                    shape=(vec.length, words)).copy() if vec.length else np.zeros((0, words), np.uint64)
+        libc.free(vec.elements)
+        return out
+    return dict(a=take(pr.a, 4), b=take(pr.b, 4), c=np.array(pr.c, np.uint64), x=np.array(pr.x, np.uint64),
+                L=take(pr.L, 16), R=take(pr.R, 16), L_len=int(pr.L_len), n=int(pr.n))
 
 
 def msm(result, scalars, points, stream=None):

@@ -161,6 +161,15 @@ struct Engine {
         Buf b[19];
     };
     std::map<hipStream_t, ProverBufs*> provers;
+    // stand-alone IPA prover workspaces (hipbp_batch_inner_product_prove), per caller stream: two
+    // chunk workspaces, the second run on an internal side stream so one chunk's latency-bound
+    // chains run under the other's scalar multiplications (the Pippenger path's scheme)
+    struct IpaBufs {
+        Buf b[2][14];
+        hipStream_t side = nullptr;
+        hipEvent_t ev[2] = {};   // [0] the caller's stream at entry, [1] the side stream's last chunk done
+    };
+    std::map<hipStream_t, IpaBufs*> ipa_ws;
     // the generators (G | H | h) a single-proof call last uploaded to h2d[4], as host bytes: the next
     // call with the same bytes (the reference's caller passes one generator set call after call)
     // skips their three pageable copies
@@ -1087,7 +1096,7 @@ int hipbp_msm_pippenger_windows(ge25519* window_sums, const fe25519* scalars, co
 }
 
 // Frees every per-stream workspace the engine keeps for `stream` on the current device (canonical
-// MSM / point-tree buffers, prover buffers, one-shot verify pipelines, Pippenger workspace pair),
+// MSM / point-tree buffers, prover buffers, IPA prover pair, one-shot verify pipelines, Pippenger pair),
 // after waiting for the stream.  A later call on that stream builds them again.
 int hipbp_release_stream_workspaces(void* stream) {
     hipError_t err;
@@ -1118,6 +1127,17 @@ int hipbp_release_stream_workspaces(void* stream) {
         free_all(pi->second->b, sizeof(pi->second->b) / sizeof(pi->second->b[0]));
         delete pi->second;
         e->provers.erase(pi);
+    }
+    auto ii = e->ipa_ws.find(s);
+    if (ii != e->ipa_ws.end()) {
+        Engine::IpaBufs* ib = ii->second;
+        if (ib->side) keep(hipStreamSynchronize(ib->side));
+        for (auto& half : ib->b) free_all(half, sizeof(half) / sizeof(half[0]));
+        for (hipEvent_t ev : ib->ev)
+            if (ev) keep(hipEventDestroy(ev));
+        if (ib->side) keep(hipStreamDestroy(ib->side));
+        delete ib;
+        e->ipa_ws.erase(ii);
     }
     for (auto it = e->pipes.begin(); it != e->pipes.end();) {
         if (std::get<0>(it->first) == s) {
@@ -1277,6 +1297,181 @@ int hipbp_batch_generate_range_proof_gens(const hipbp_prove_input* in, void* gen
     if (dev != gs->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
     return prove_run(in, (const ge25519*)gs->G(), (const ge25519*)gs->H(), (const ge25519*)gs->g(),
                      (const ge25519*)gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits, out, stream);
+}
+
+// ---- stand-alone IPA prover (bp_ipa_prove.hip).  The engine's lock is held by the caller.
+// `count` is cut into chunks sized from a workspace budget (HIPBP_IPA_WS_MB per workspace, default
+// 512: ~1.8 MB per proof at n = 4096) that alternate over two workspaces: even chunks on the
+// caller's stream, odd ones on the internal side stream; the caller's stream waits for the side
+// stream at the end.  A chunk's chain latency does not depend on its size, so the fewest chunks
+// that fit are used (two whenever count >= 2).
+static int ipa_enqueue(Engine& e, const hipbp_ipa_prove_input* in, const bp::ge* G, const bp::ge* H, const bp::ge* Q,
+                       const bp::ge* ptab, int pbits, const hipbp_ipa_proof_out* out, hipStream_t s) {
+    const size_t B = in->count, n = in->n;
+    const int Lr = log2i(n);
+    const size_t FE = sizeof(bp::fe), GE = sizeof(bp::ge), cap = 2 * n + 2;
+    // per proof: a, b, prod [n], sc [2n], csc [2], tr, uu [2], x | term [2n], cq [2], chain [4] | slist, llist [cap]
+    const size_t per_proof = (5 * n + 6) * FE + (2 * n + 6) * GE + 2 * cap * sizeof(uint32_t);
+    const char* env = getenv("HIPBP_IPA_WS_MB");
+    size_t mb = env ? (size_t)atoll(env) : 512;
+    if (mb < 1) mb = 1;
+    size_t bmax = std::max<size_t>(1, (mb << 20) / per_proof);
+    bmax = std::min(bmax, (size_t)0x7FFFFFFF / cap);   // item ids are 32-bit
+    const size_t chunks = std::max((B + bmax - 1) / bmax, std::min<size_t>(B, 2));
+    const size_t Bc = (B + chunks - 1) / chunks;
+    Engine::IpaBufs*& ib = e.ipa_ws[s];
+    if (!ib) ib = new Engine::IpaBufs();
+    if (chunks > 1 && !ib->side) {
+        BP_RET_ON(hipStreamCreateWithFlags(&ib->side, hipStreamNonBlocking));
+        for (auto& ev : ib->ev) BP_RET_ON(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    const size_t sz[14] = {Bc * n * FE, Bc * n * FE, Bc * n * FE, Bc * 2 * n * FE, Bc * 2 * FE, Bc * 2 * n * GE,
+                           Bc * 2 * GE, Bc * 4 * GE, Bc * FE, Bc * 2 * FE, Bc * FE, Bc * cap * sizeof(uint32_t),
+                           Bc * cap * sizeof(uint32_t), (bp::MSM_BINS + 2) * sizeof(unsigned)};
+    for (size_t w = 0; w < std::min<size_t>(chunks, 2); w++)
+        for (int i = 0; i < 14; i++) BP_RET_ON(ib->b[w][i].need(sz[i]));
+    if (chunks > 1) {   // the side stream starts after the caller's queued work (the inputs' producers)
+        BP_RET_ON(hipEventRecord(ib->ev[0], s));
+        BP_RET_ON(hipStreamWaitEvent(ib->side, ib->ev[0], 0));
+    }
+    const bp::fe *ia = (const bp::fe*)in->a, *ibv = (const bp::fe*)in->b, *ic = (const bp::fe*)in->c,
+                 *itr = (const bp::fe*)in->transcript;
+    for (size_t c = 0; c < chunks; c++) {
+        const size_t p0 = c * Bc;
+        if (p0 >= B) break;
+        const size_t bc = std::min(Bc, B - p0);
+        Buf* w = ib->b[c & 1];
+        hipStream_t st = (c & 1) ? ib->side : s;
+        bp::IpaWs ws{(int)bc, (int)n, Lr, w[0].as<bp::fe>(), w[1].as<bp::fe>(), w[2].as<bp::fe>(), w[3].as<bp::fe>(),
+                     w[4].as<bp::fe>(), w[5].as<bp::ge>(), w[6].as<bp::ge>(), w[7].as<bp::ge>(), w[8].as<bp::fe>(),
+                     w[9].as<bp::fe>(), w[10].as<bp::fe>(), w[11].as<uint32_t>(), w[12].as<uint32_t>(),
+                     w[13].as<unsigned>(), Lr ? (bp::ge*)out->L + p0 * Lr : nullptr,
+                     Lr ? (bp::ge*)out->R + p0 * Lr : nullptr, ptab, ptab ? pbits : 0};
+        bp::launch_ipa_load(ws, ia + p0 * n, ibv + p0 * n, itr ? itr + p0 : nullptr, st);
+        for (int r = 0; r < Lr; r++) bp::launch_ipa_round(ws, r, G, H, Q, e.dtab, st);
+        bp::launch_ipa_final(ws, ic + p0, (bp::fe*)out->a + p0, (bp::fe*)out->b + p0, (bp::fe*)out->c + p0,
+                             (bp::fe*)out->x + p0, out->c_final ? (bp::fe*)out->c_final + p0 : nullptr, st);
+        BP_RET_ON(hipGetLastError());
+    }
+    if (chunks > 1) {
+        BP_RET_ON(hipEventRecord(ib->ev[1], ib->side));
+        BP_RET_ON(hipStreamWaitEvent(s, ib->ev[1], 0));
+    }
+    return HIPBP_OK;
+}
+
+static int ipa_check(const hipbp_ipa_prove_input* in, const hipbp_ipa_proof_out* out) {
+    if (!in || !out) { g_err = "ipa prover: null argument"; return HIPBP_ERR_ARG; }
+    if (!is_pow2(in->n) || in->n > MAX_N) { g_err = "ipa prover: n must be a power of two <= 65536"; return HIPBP_ERR_ARG; }
+    if (in->count > ((size_t)1 << 24)) { g_err = "ipa prover: batch too large"; return HIPBP_ERR_ARG; }
+    if (!in->a || !in->b || !in->c) { g_err = "ipa prover: null input"; return HIPBP_ERR_ARG; }
+    if (!out->a || !out->b || !out->c || !out->x || (in->n > 1 && (!out->L || !out->R))) {
+        g_err = "ipa prover: null output";
+        return HIPBP_ERR_ARG;
+    }
+    return HIPBP_OK;
+}
+
+int hipbp_batch_inner_product_prove(const hipbp_ipa_prove_input* in, const ge25519* G, const ge25519* H,
+                                    const ge25519* Q, hipbp_ipa_proof_out* out, void* stream) {
+    hipError_t err;
+    Engine* e = engine_or_null(&err);
+    BP_RET_ON(err);
+    if (!G || !H || !Q) { g_err = "ipa prover: null generator"; return HIPBP_ERR_ARG; }
+    if (int rc = ipa_check(in, out)) return rc;
+    if (in->count == 0) return HIPBP_OK;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return ipa_enqueue(*e, in, (const bp::ge*)G, (const bp::ge*)H, (const bp::ge*)Q, nullptr, 0, out,
+                       pick(stream, *e));
+}
+
+int hipbp_batch_inner_product_prove_gens(const hipbp_ipa_prove_input* in, void* gens, hipbp_ipa_proof_out* out,
+                                         void* stream) {
+    hipError_t err;
+    Engine* e = engine_or_null(&err);
+    BP_RET_ON(err);
+    Gens* gs = (Gens*)gens;
+    if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
+    if (int rc = ipa_check(in, out)) return rc;
+    if (in->n != gs->n) { g_err = "ipa prover: input n differs from the generator set's"; return HIPBP_ERR_ARG; }
+    if (gs->device != e->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    if (in->count == 0) return HIPBP_OK;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return ipa_enqueue(*e, in, gs->G(), gs->H(), gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits, out,
+                       pick(stream, *e));
+}
+
+// inner_product_prove (bulletproof_vectors.cu:277) on the reference's own host structs: its two
+// checks with its messages (the proof is left untouched), then one proof through the batched
+// prover on the engine's stream, synchronously; the proof's vectors are malloc'ed as
+// inner_product_proof_init / field_vector_copy leave them (a, b of length 1, L, R of log2 n).
+int hipbp_inner_product_prove_host(InnerProductProof* proof, const FieldVector* a, const FieldVector* b,
+                                   const PointVector* G, const PointVector* H, const ge25519* Q,
+                                   const fe25519* c_in, const uint8_t* transcript32) {
+    if (!proof || !a || !b || !G || !H || !Q || !c_in) { g_err = "ipa prover: null argument"; return HIPBP_ERR_ARG; }
+    if (a->length != b->length || a->length != G->length || a->length != H->length) {   // vectors.cu:288-291
+        fprintf(stderr, "Error: Vector lengths must match for inner product proof\n");
+        return HIPBP_ERR_ARG;
+    }
+    const size_t n = a->length;
+    if (!is_pow2(n)) {                                                                  // vectors.cu:295-298
+        fprintf(stderr, "Error: Inner product proof length must be a power of 2\n");
+        return HIPBP_ERR_ARG;
+    }
+    if (n > MAX_N) { g_err = "ipa prover: n must be a power of two <= 65536"; return HIPBP_ERR_ARG; }
+    Engine& e = engine_or_exit();
+    std::lock_guard<std::mutex> lk(e.mu);
+    const size_t FE = sizeof(fe25519), GE = sizeof(ge25519), Lr = (size_t)log2i(n);
+    // device staging: G | H | Q | L | R (points), then a | b | c | transcript | out a, b, c, x
+    BP_EXIT_ON(e.scratch[4].need((2 * n + 1 + 2 * Lr) * GE + (2 * n + 6) * FE));
+    ge25519* dG = e.scratch[4].as<ge25519>();
+    ge25519 *dH = dG + n, *dQ = dH + n, *dL = dQ + 1, *dR = dL + Lr;
+    fe25519* da = (fe25519*)(dR + Lr);
+    fe25519 *db = da + n, *dc = db + n, *dt = dc + 1, *oa = dt + 1;
+    hipStream_t s = e.stream;
+    BP_EXIT_ON(hipMemcpyAsync(dG, G->elements, n * GE, hipMemcpyHostToDevice, s));
+    BP_EXIT_ON(hipMemcpyAsync(dH, H->elements, n * GE, hipMemcpyHostToDevice, s));
+    BP_EXIT_ON(hipMemcpyAsync(dQ, Q, GE, hipMemcpyHostToDevice, s));
+    BP_EXIT_ON(hipMemcpyAsync(da, a->elements, n * FE, hipMemcpyHostToDevice, s));
+    BP_EXIT_ON(hipMemcpyAsync(db, b->elements, n * FE, hipMemcpyHostToDevice, s));
+    BP_EXIT_ON(hipMemcpyAsync(dc, c_in, FE, hipMemcpyHostToDevice, s));
+    if (transcript32) BP_EXIT_ON(hipMemcpyAsync(dt, transcript32, FE, hipMemcpyHostToDevice, s));
+    hipbp_ipa_prove_input in{1, n, da, db, dc, transcript32 ? dt : nullptr};
+    hipbp_ipa_proof_out out{oa, oa + 1, oa + 2, oa + 3, nullptr, dL, dR};
+    if (ipa_enqueue(e, &in, (const bp::ge*)dG, (const bp::ge*)dH, (const bp::ge*)dQ, nullptr, 0, &out, s) != HIPBP_OK) {
+        fprintf(stderr, "HIP error in inner_product_prove - %s\n", g_err.c_str());
+        exit(EXIT_FAILURE);
+    }
+    fe25519 res[4];
+    fe25519* ha = (fe25519*)malloc(FE);
+    fe25519* hb = (fe25519*)malloc(FE);
+    ge25519* hL = (ge25519*)malloc(Lr ? Lr * GE : 1);
+    ge25519* hR = (ge25519*)malloc(Lr ? Lr * GE : 1);
+    if (!ha || !hb || !hL || !hR) {
+        fprintf(stderr, "Error: Failed to allocate memory for field vector\n");
+        exit(1);
+    }
+    BP_EXIT_ON(hipMemcpyAsync(res, oa, 4 * FE, hipMemcpyDeviceToHost, s));
+    if (Lr) {
+        BP_EXIT_ON(hipMemcpyAsync(hL, dL, Lr * GE, hipMemcpyDeviceToHost, s));
+        BP_EXIT_ON(hipMemcpyAsync(hR, dR, Lr * GE, hipMemcpyDeviceToHost, s));
+    }
+    BP_EXIT_ON(hipStreamSynchronize(s));
+    *ha = res[0];
+    *hb = res[1];
+    proof->n = n;
+    proof->a.elements = ha;
+    proof->a.length = 1;
+    proof->b.elements = hb;
+    proof->b.length = 1;
+    proof->c = res[2];
+    proof->L.elements = hL;
+    proof->L.length = Lr;
+    proof->R.elements = hR;
+    proof->R.length = Lr;
+    proof->L_len = Lr;
+    proof->x = res[3];
+    return HIPBP_OK;
 }
 
 int hipbp_pipeline_use_gens(void* handle, void* gens) {

@@ -317,6 +317,36 @@ enum ProveStage { PS_PREP = 0, PS_TERMS0, PS_CHAIN0, PS_COMMIT, PS_TERMS1, PS_TX
 void launch_prove(int stage, int r, const ProveIn& in, const ProveWs& ws, const ProveOut& out, const ge* G,
                   const ge* H, const ge* g, const ge* h, const ge* dtab, const fe* two_i, hipStream_t s);
 
+// ------------------------------------------------------------------ stand-alone IPA prover (bp_ipa_prove.hip)
+// Workspace of one chunk of inner_product_prove calls (hipbp_batch_inner_product_prove): B proofs of
+// n elements each.  Item k < 4n' + 2 of proof p in round r (n' = n >> (r + 1)): the MSM terms
+// a_L_j G[n'+j] | b_R_j H[j] | a_R_j G[j] | b_L_j H[n'+j], then c_L Q, c_R Q; its id is p (4n' + 2) + k.
+struct IpaWs {
+    int B, n, Lr;     // proofs of the chunk, vector length, rounds (log2 n)
+    fe* a;            // [B*n]   a, folded in place (the live half shrinks round by round)
+    fe* b;            // [B*n]
+    fe* prod;         // [B*n]   round products: a_L_j b_R_j at p n + j, a_R_j b_L_j at p n + n' + j
+    fe* sc;           // [B*2n]  the round's MSM scalars in tobytes form, p 2n + k
+    fe* csc;          // [B*2]   c_L, c_R (tobytes form)
+    ge* term;         // [B*2n]  the round's MSM terms (host-normalized), p 2n + k
+    ge* cq;           // [B*2]   c_L Q, c_R Q (raw)
+    ge* chain;        // [B*4]   the four sequential MSM accumulations
+    fe* tr;           // [B]     transcript (raw limbs)
+    fe* uu;           // [B*2]   the round's u, u^-1
+    fe* x;            // [B]     the first round's u (0 when n = 1)
+    uint32_t* slist;  // [B*(2n+2)] heavy items (> 64-bit scalars) in chain-length order, longest first
+    uint32_t* llist;  // [B*(2n+2)] light items
+    unsigned* ctl;    // [MSM_BINS + 2] chain-length bins / start offsets, heavy count, light count
+    ge* L;            // [B*Lr]  the caller's L, R at this chunk's first proof
+    ge* R;
+    const ge* ptab;   // fixed-base prefix tables (nullable; the SlotDev::ptab layout, Q = the set's h)
+    int pbits;
+};
+void launch_ipa_load(const IpaWs& ws, const fe* a, const fe* b, const fe* tr /* nullable: zeros */, hipStream_t s);
+void launch_ipa_round(const IpaWs& ws, int r, const ge* G, const ge* H, const ge* Q, const ge* dtab, hipStream_t s);
+void launch_ipa_final(const IpaWs& ws, const fe* c_in, fe* a, fe* b, fe* c, fe* x, fe* c_final /* nullable */,
+                      hipStream_t s);
+
 // Elementwise field ops: op 0 add, 1 sub, 2 mul, 3 square-kernel quirk, 4 soa add (limbwise, no carry)
 void launch_field_op(int op, fe* r, const fe* a, const fe* b, size_t count, hipStream_t s);
 void launch_sha_probe(int kind, fe* out, const fe* in, size_t count, hipStream_t s);

@@ -249,6 +249,49 @@ int hipbp_batch_generate_range_proof(const hipbp_prove_input* in, const ge25519*
 int hipbp_batch_generate_range_proof_gens(const hipbp_prove_input* in, void* gens, hipbp_proof_out* out,
                                           void* stream);
 
+/* ---- prover: the stand-alone inner_product_prove (bulletproof_vectors.h:94,
+ * bulletproof_vectors.cu:277-523) for any power-of-two length, batched, bit-exact: the reference's
+ * sequential MSM chains and inner products in its order, the ORIGINAL G, H in every round, Q any
+ * point, the transcript's 32 bytes as raw limbs, proof.c = the claimed c as given.  Every O(n)
+ * piece of a round runs one lane per element or term; only the order-bound addition chains run one
+ * lane per chain.  `count` is processed in chunks that alternate over two internal workspaces, the
+ * second on an internal side stream (one chunk's chains run under the other's scalar
+ * multiplications); the caller's stream waits for it at the end, so the outputs are ready in the
+ * caller's stream order.  HIPBP_IPA_WS_MB: the per-workspace budget that sizes a chunk (default 512).
+ * All pointers DEVICE memory; asynchronous on `stream`.  A bad n or a null pointer gives
+ * HIPBP_ERR_ARG and writes nothing. */
+typedef struct {
+    size_t count, n;              /* n: power of two, 1..65536 */
+    const fe25519 *a, *b;         /* [count*n] */
+    const fe25519 *c;             /* [count] the claimed c_in */
+    const fe25519 *transcript;    /* [count] 32 initial transcript bytes as 4 LE limbs; NULL = zeros */
+} hipbp_ipa_prove_input;
+/* Output in the verifier's wire format (ab_len = 1, L_len = log2 n): with P = hipbp_msm_batch(a||b,
+ * G||H) it goes straight into hipbp_batch_inner_product_verify.  n = 1: no rounds, a, b copies of
+ * the inputs, x = 0. */
+typedef struct {
+    fe25519 *a, *b, *c, *x;       /* [count]: final length-1 a, b; c = c_in; x = first challenge */
+    fe25519 *c_final;             /* nullable: add(0, mul(a, b)) of the final a, b — the c with which the
+                                   * reference's verifier accepts (it compares c with <a, b> first) */
+    ge25519 *L, *R;               /* [count*log2 n]; may be NULL when n = 1 */
+} hipbp_ipa_proof_out;
+int hipbp_batch_inner_product_prove(const hipbp_ipa_prove_input* in, const ge25519* G, const ge25519* H,
+                                    const ge25519* Q, hipbp_ipa_proof_out* out, void* stream);
+/* The same with a generator set's G, H and prefix tables (same n, same device), Q = its h; the same
+ * bits as the plain form on those generators. */
+int hipbp_batch_inner_product_prove_gens(const hipbp_ipa_prove_input* in, void* gens, hipbp_ipa_proof_out* out,
+                                         void* stream);
+/* inner_product_prove on the reference's own host structs (host pointers, synchronous, one proof):
+ * on a length mismatch or a length that is no power of two it prints the reference's message on
+ * stderr and leaves *proof untouched (HIPBP_ERR_ARG); otherwise *proof is filled as the reference
+ * leaves it: a, b of length 1, L, R of L_len = log2 n, all malloc'ed, so inner_product_proof_free
+ * frees them.  Unlike the reference it does not print the inner products.  A reference user renames
+ * the call; the name inner_product_prove itself is not exported (the reference's host code defines
+ * it and links against this library). */
+int hipbp_inner_product_prove_host(InnerProductProof* proof, const FieldVector* a, const FieldVector* b,
+                                   const PointVector* G, const PointVector* H, const ge25519* Q,
+                                   const fe25519* c_in, const uint8_t* transcript32 /* NULL = zeros */);
+
 /* Canonical-tree MSM on device buffers.  Asynchronous on `stream`; the MSM, MSM-batch
  * and point-tree calls keep one workspace per (device, stream), so calls on different streams may
  * run concurrently. */
@@ -319,8 +362,8 @@ int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_
  * in0..in3 in raw limb order.  For checking against FIPS 180-4 (bulletproof_challenge.cu:6-77). */
 int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
- * point-tree, prover, one-shot verify pipelines, the Pippenger workspace pair with its side stream
- * and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
+ * point-tree, prover, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
+ * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
  * a caller that makes short-lived streams calls this before destroying one.  No reference
  * counterpart. */
 int hipbp_release_stream_workspaces(void* stream);
