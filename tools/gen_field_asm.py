@@ -6,15 +6,33 @@ Why asm: the fix-up "(carry || h >= p) ? lossy - p : h" is a data-dependent sele
 C the compiler materialises each mask with v_cmp + v_cndmask (4.5-4.6 cycles per wave
 instruction, tools/ubench_enc.hip) and adds through 64-bit v_lshl_add_u64 (4.7); here the masks
 stay in SGPRs, are combined by SALU (its own issue port) and enter the arithmetic as the carry-ins
-of v_addc.  Every operand is a 32-bit VGPR: the C side passes limb halves (free sub-registers),
-so no register pair has to be formed.
+of v_addc.  The chains' operands are 32-bit VGPRs: the C side passes limb halves (free
+sub-registers).
+
+The fast fix-up (what every fold, add and fused add/sub ends with unless a lane is on a rare edge) is
+h += m (19, 0, 1, 2^63) with m = carry | bit 255, in 5 VALU: m1 = m as a word (v_lshrrev_b32 of h7,
+v_cndmask_b32 on the carry: fix_m1), then limb 0 += 19 m1 as one v_mad_u64_u32 on the register
+pair, h4 += m1 and h7 += m1 << 31 (v_lshl_add_u32) (FIX_FAST).  There is no link from h4 into h5:
+the fast form runs only when the rare-edge test (fix_test) found no lane with max(h1, h4) == 2^32-1,
+so h4 + m1 cannot carry out.  Limb 0 needs an even-aligned pair, which an asm operand can only be
+as a whole, so the three additions are a second statement (emit_fixups) whose 64-bit "+v" operand the
+C glue packs from h0 and h1: the compiler allocates the chain's two outputs into the pair directly.
+fe25519_sub's fast "+ p", t += m (-19, 0, 0, 2^63), is the same shape: mn = -m by one v_cndmask_b32,
+limb 0 += 19 mn as one v_mad_i64_i32, h7 += mn << 31 (SUBP_FAST), 3 VALU where the 32-bit form took
+5; its links never went past limb 0 (the test excludes t0 < 19), so nothing else could be dropped.
+No form needs 0x80000000 in a register any more.  The throughput and the latency forms (the row
+step's, which avoided a compare + SALU OR on the carry) are now the same instructions: both names
+are kept because the callers select by them.  fe_canon_asm keeps its two paths in one statement, so
+its fast path is the 32-bit rendering of the same fix-up (fix_fast32, 6 VALU).
 
 Hazard rule these sequences meet (gfx950): an SGPR written by a VALU instruction (carry-out,
 v_cmp) and read by a VALU instruction as a mask or source operand (v_cndmask) needs 2 wait states
 in between, read as a carry-in (v_addc / v_subb) 1 wait state, the spacing the compiler itself
 gives the same e64 carry chains (tools/hazard_probe.hip read no stale carry even at 0 on MI355X);
 SALU-written masks can be read at once.  `schedule` inserts the s_nop.  Outputs are VGPRs only,
-inputs are VGPRs or constants, so nothing crosses the asm boundary in an SGPR.
+inputs are VGPRs or constants, so nothing crosses the asm boundary in an SGPR (m1 and mn are VGPR
+words for that reason).  The carry-out pair that v_mad_u64_u32 / v_mad_i64_i32 must name is an
+early-clobber temporary nothing reads.
 """
 import os
 
@@ -117,53 +135,82 @@ def fix_seq(h, o, carry):
 FIX_SGPRS = ["sf1", "sf2", "se3", "stp", "sg0", "sg1", "sm", "sd1", "sd2", "sd3", "sk0", "sk1", "sk2", "sk3"]
 
 
-def fix_test(h, carry):
+def fix_test(h):
     """Wave-uniform test for fix_seq's fast form.  With h0 < P0 (br1 = 1) the fix-up's m is
     carry | top (the equality case needs h0 >= P0), br2 = 0 and br3 = !(h2 == M), so when also
     h2 != M every lane's result is h + m (19, 0, 1, 2^63).  h0 >= P0 implies h0's high word is
     2^32-1 and h2 == M implies its low word is: srare = max(those words) == 2^32-1 is a superset of
-    the lanes that need the exact form.  Also forms m = carry | top in sm."""
+    the lanes that need the exact form.  The same test excludes h4 == 2^32-1, so on the fast path
+    limb 2's "+ m" cannot carry out of its low word: the fast fix-up has no link into h5."""
     return [V(f"v_max_u32 %[vt3], %[{h[1]}], %[{h[4]}]"),
-            V(f"v_cmp_gt_i32 %[stp], 0, %[{h[7]}]", ["stp"]),
-            V("v_cmp_eq_u32 %[srare], -1, %[vt3]", ["srare"]),
-            S(f"s_or_b64 %[sm], {cref(carry)}, %[stp]", ["sm"])]
+            V("v_cmp_eq_u32 %[srare], -1, %[vt3]", ["srare"])]
 
 
-def fix_fast(h):
-    """h += m (19, 0, 1, 2^63) per limb, in place (valid when fix_test found no rare lane)."""
-    return [V("v_cndmask_b32 %[vt1], 0, 19, %[sm]", [], ["sm"]),
-            V("v_cndmask_b32 %[vt2], 0, %[c80], %[sm]", [], ["sm"]),
-            V(f"v_add_co_u32 %[{h[0]}], %[sk0], %[{h[0]}], %[vt1]", ["sk0"]),
-            V(f"v_addc_co_u32 %[{h[4]}], %[sk2], %[{h[4]}], 0, %[sm]", ["sk2"], ["sm"]),
-            V(f"v_add_u32 %[{h[7]}], %[{h[7]}], %[vt2]"),
-            V(f"v_addc_co_u32 %[{h[1]}], %[sk0], %[{h[1]}], 0, %[sk0]", ["sk0"], ["sk0"]),
-            V(f"v_addc_co_u32 %[{h[5]}], %[sk2], %[{h[5]}], 0, %[sk2]", ["sk2"], ["sk2"])]
+def fix_m1(h, carry="scy", m1="vt1"):
+    """m1 = carry | bit 255 as a VGPR word, 0 or 1: the tail of every fast statement.  The carry is
+    read as a mask straight from the chain's last link (WAIT_MASK after it), so the throughput and
+    the latency forms are one: no compare, no SALU OR for a lone wave to wait on."""
+    return [V(f"v_lshrrev_b32 %[{m1}], 31, %[{h[7]}]"),
+            V(f"v_cndmask_b32 %[{m1}], %[{m1}], 1, %[{carry}]", [], [carry])]
 
 
-def fix_fast_lat(h, carry="scy"):
-    """fix_fast for the latency forms (the 16-lane row step): m = carry | top as a VALU mask, 0 or
-    -1, instead of a compare and the SALU OR, which waits ≈16 cycles on that compare when one wave
-    runs alone (tools/ubench_dep.hip cmp_sor_add).  Two more VALU than fix_fast's compare and two
-    selects: a loss where many waves hide the wait (the throughput kernels keep fix_fast)."""
-    return [V(f"v_ashrrev_i32 %[vt2], 31, %[{h[7]}]"),
-            V(f"v_cndmask_b32 %[vt2], %[vt2], -1, %[{carry}]", [], [carry]),
-            V("v_and_b32 %[vt1], 19, %[vt2]"),
-            V("v_lshrrev_b32 %[vt3], 31, %[vt2]"),
-            V("v_and_b32 %[vt2], %[c80], %[vt2]"),
-            V(f"v_add_co_u32 %[{h[0]}], %[sk0], %[{h[0]}], %[vt1]", ["sk0"]),
-            V(f"v_add_co_u32 %[{h[4]}], %[sk2], %[{h[4]}], %[vt3]", ["sk2"]),
-            V(f"v_add_u32 %[{h[7]}], %[{h[7]}], %[vt2]"),
-            V(f"v_addc_co_u32 %[{h[1]}], %[sk0], %[{h[1]}], 0, %[sk0]", ["sk0"], ["sk0"]),
-            V(f"v_addc_co_u32 %[{h[5]}], %[sk2], %[{h[5]}], 0, %[sk2]", ["sk2"], ["sk2"])]
+FIX_FAST = ["v_mad_u64_u32 %[l0], %[sd], %[m1], 19, %[l0]",   # limb 0 += 19 m (sd: a carry-out nothing reads)
+            "v_add_u32 %[h4], %[h4], %[m1]",                    # limb 2's low word += m
+            "v_lshl_add_u32 %[h7], %[m1], 31, %[h7]"]           # limb 3 += m 2^63
+SUBP_FAST = ["v_mad_i64_i32 %[l0], %[sd], %[mn], 19, %[l0]",    # limb 0 -= 19 m (mn = -m)
+             "v_lshl_add_u32 %[h7], %[mn], 31, %[h7]"]          # limb 3 += m 2^63
+
+
+def fix_fast32(h):
+    """fix_m1 + FIX_FAST on 32-bit words, for fe_canon_asm: its fast and exact forms share one
+    statement whose operands are the eight words, so limb 0 cannot be named as a register pair.
+    Limb 0's add stays an add / add-with-carry pair; the h5 link is dropped as in FIX_FAST."""
+    return [V(f"v_lshrrev_b32 %[vt1], 31, %[{h[7]}]"),
+            V("v_mul_u32_u24 %[vt2], 19, %[vt1]"),
+            V(f"v_add_co_u32 %[{h[0]}], %[sk0], %[{h[0]}], %[vt2]", ["sk0"]),
+            V(f"v_add_u32 %[{h[4]}], %[{h[4]}], %[vt1]"),
+            V(f"v_lshl_add_u32 %[{h[7]}], %[vt1], 31, %[{h[7]}]"),
+            V(f"v_addc_co_u32 %[{h[1]}], %[sk0], %[{h[1]}], 0, %[sk0]", ["sk0"], ["sk0"])]
+
+
+def emit_fixups():
+    """The fast fix-ups as statements of their own (FIX_FAST, SUBP_FAST): limb 0 enters as a 64-bit
+    operand, which the compiler places in an aligned register pair."""
+    out = ["// The fast fix-up h += m (19, 0, 1, 2^63), m1 = m as 0 or 1 (tools/gen_field_asm.py FIX_FAST): limb 0 as",
+           "// a register pair, limb 2's low word and limb 3's high word.  Valid when the rare-edge test found no lane.",
+           "__device__ __forceinline__ void fe_fix_fast_asm(uint32_t& h0, uint32_t& h1, uint32_t& h4, uint32_t& h7, uint32_t m1) {",
+           "    uint64_t l0 = (uint64_t)h0 | ((uint64_t)h1 << 32), sd;",
+           '    asm("{0}"'.format("\\n\\t".join(FIX_FAST)),
+           '                 : [l0] "+v"(l0), [h4] "+v"(h4), [h7] "+v"(h7), [sd] "=&s"(sd)',
+           '                 : [m1] "v"(m1));',
+           "    h0 = (uint32_t)l0; h1 = (uint32_t)(l0 >> 32);",
+           "    (void)sd;",
+           "}",
+           "// The fast \"+ p\" of fe25519_sub, t += m (-19, 0, 0, 2^63), mn = -m as 0 or -1 (SUBP_FAST).",
+           "__device__ __forceinline__ void fe_subp_fast_asm(uint32_t& h0, uint32_t& h1, uint32_t& h7, uint32_t mn) {",
+           "    uint64_t l0 = (uint64_t)h0 | ((uint64_t)h1 << 32), sd;",
+           '    asm("{0}"'.format("\\n\\t".join(SUBP_FAST)),
+           '                 : [l0] "+v"(l0), [h7] "+v"(h7), [sd] "=&s"(sd)',
+           '                 : [mn] "v"(mn));',
+           "    h0 = (uint32_t)l0; h1 = (uint32_t)(l0 >> 32);",
+           "    (void)sd;",
+           "}"]
+    return out
+
+
+ADD_POST = ["fe_fix_fast_asm(h0, h1, h4, h7, vt1);"]
+SUB_POST = ["fe_subp_fast_asm(h0, h1, h7, vt1);"]
+ADDSUB_POST = ["fe_fix_fast_asm(h0, h1, h4, h7, vt1);", "fe_subp_fast_asm(t0, t1, t7, vt4);"]
 
 
 def branch_if_rare(label):
     return [S("s_cmp_lg_u64 %[srare], 0"), S(f"s_cbranch_scc1 {label}")]
 
 
-def emit(name, doc, args, ins, outs, vtemps, sgprs, lines, inout=False):
+def emit(name, doc, args, ins, outs, vtemps, sgprs, lines, inout=False, c80=True):
     """args: [(param, prefix)] array params bound to scalars prefix0..7.  lines: scheduled asm.
-    inout: the outputs are read-write, initialised from the first array argument."""
+    inout: the outputs are read-write, initialised from the first array argument.
+    c80: bind the constant 0x80000000 as a VGPR input (the compiler materialises it before the block)."""
     # No trailing wait states (rounds 2-6 ended every block with s_nop 4 against "a VALU SGPR write
     # followed by a VMEM read of it needs 5").  The block's SGPR outputs are early-clobber temporaries
     # that nothing reads after it, so any later read of those registers follows a new write of them
@@ -186,7 +233,7 @@ def emit(name, doc, args, ins, outs, vtemps, sgprs, lines, inout=False):
                                           [f'[{x}] "=&v"({x})' for x in vtemps] +
                                           [f'[{x}] "=&s"({x})' for x in sgprs]))
     out.append("                 : " + ", ".join([f'[{x}] "v"({x})' for x in ins] +
-                                          ['[c80] "v"(0x80000000u)', '[p0l] "s"(0xFFFFFFEDu)']))
+                                          (['[c80] "v"(0x80000000u)'] if c80 else []) + ['[p0l] "s"(0xFFFFFFEDu)']))
     # the SALU mask logic overwrites SCC; without the clobber the compiler keeps a compare's SCC
     # live across the block (seen: s_cmp before the block, s_cbranch_scc1 after it)
     out.append('                 : "scc");')
@@ -207,16 +254,21 @@ def two_way(pre, fast, slow):
     return lp + lf + ["s_branch 4f", "3:"] + ls + ["4:"]
 
 
-def emit_split(name, doc, args, outs, vtemps, fast_sgprs, fast, slow_sgprs, slow):
+def emit_split(name, doc, args, outs, vtemps, fast_sgprs, fast, slow_sgprs, slow, post, fast_vtemps):
     """The fast form and the exact form as two asm statements: the fast one computes the common result
     and the wave-uniform rare-edge mask srare; the exact one (from the inputs again) runs under a C
     branch the compiler places out of line.  Measured on one wave (tools/ubench_dep.hip,
     profiles/ubench/ubench_dep_r06.json): a compare read by the SALU test right after it stalls the
     wave ~20 cycles and the taken s_branch over an inline exact form costs ~22; srare is written
     early in the fast statement, so the test after it finds it ready, and the common path falls
-    through (a not-taken branch, ~8 cycles)."""
+    through (a not-taken branch, ~8 cycles).
+    post: the fast fix-up's statements (emit_fixups), C calls on the fast statement's words and its
+    m words; they run before the branch, and the exact statement writes every word again.  The fast
+    statement binds only the temporaries it uses (fast_vtemps) and no constant."""
     ins = [f"{pre}{i}" for _, pre in args for i in range(8)]
     outs_c = [f'[{x}] "=&v"({x})' for x in outs + vtemps]
+    fast_c = [f'[{x}] "=&v"({x})' for x in outs + fast_vtemps]
+    fast_ins_c = ", ".join(f'[{x}] "v"({x})' for x in ins)
     ins_c = ", ".join([f'[{x}] "v"({x})' for x in ins] + ['[c80] "v"(0x80000000u)', '[p0l] "s"(0xFFFFFFEDu)'])
     out = [f"// {d}" for d in doc]
     out.append(f"__device__ __forceinline__ void {name}(" + ", ".join(f"uint32_t o{k}[8]" for k in range(len(outs) // 8)) +
@@ -226,9 +278,9 @@ def emit_split(name, doc, args, outs, vtemps, fast_sgprs, fast, slow_sgprs, slow
     out.append("    uint32_t " + ", ".join(outs + vtemps) + ";")
     out.append("    uint64_t " + ", ".join(fast_sgprs) + ";")
     out.append('    asm volatile("{0}"'.format("\\n\\t".join(fast)))
-    out.append("                 : " + ", ".join(outs_c + [f'[{x}] "=&s"({x})' for x in fast_sgprs]))
-    out.append("                 : " + ins_c)
-    out.append('                 : "scc");')
+    out.append("                 : " + ", ".join(fast_c + [f'[{x}] "=&s"({x})' for x in fast_sgprs]))
+    out.append("                 : " + fast_ins_c + ");")
+    out += ["    " + c for c in post]
     out.append("    if (__builtin_expect(srare != 0, 0)) {   // some lane is on a rare edge: the exact form")
     out.append("        uint64_t " + ", ".join(slow_sgprs) + ";")
     out.append('        asm volatile("{0}"'.format("\\n\\t".join(slow)))
@@ -244,11 +296,12 @@ def emit_split(name, doc, args, outs, vtemps, fast_sgprs, fast, slow_sgprs, slow
     return out
 
 
-def emit_acc(name, doc, args, outs, vtemps, sgprs, fast):
+def emit_acc(name, doc, args, outs, vtemps, sgprs, fast, post):
     """The fast statement alone, for callers that defer the rare-edge test (the row step): the words
     the test reads go into the caller's running max `acc` (v_max_u32 in place of the compare); a
     rare lane shows as acc == 2^32-1 and the caller recomputes the whole step with the exact-capable
-    forms.  Same VALU count as the fast statement of emit_split, no SALU test, no branch."""
+    forms.  Same VALU count as the fast statement of emit_split, no SALU test, no branch; then the
+    same fast fix-up statements (post)."""
     ins = [f"{pre}{i}" for _, pre in args for i in range(8)]
     out = [f"// {d}" for d in doc]
     out.append(f"__device__ __forceinline__ void {name}(" + ", ".join(f"uint32_t o{k}[8]" for k in range(len(outs) // 8)) +
@@ -260,8 +313,8 @@ def emit_acc(name, doc, args, outs, vtemps, sgprs, fast):
     out.append('    asm volatile("{0}"'.format("\\n\\t".join(fast)))
     out.append("                 : " + ", ".join([f'[{x}] "=&v"({x})' for x in outs + vtemps] + ['[acc] "+v"(acc)'] +
                                           [f'[{x}] "=&s"({x})' for x in sgprs]))
-    out.append("                 : " + ", ".join([f'[{x}] "v"({x})' for x in ins] + ['[c80] "v"(0x80000000u)']))
-    out.append('                 : "scc");')
+    out.append("                 : " + ", ".join(f'[{x}] "v"({x})' for x in ins) + ");")
+    out += ["    " + c for c in post]
     for k in range(len(outs) // 8):
         out.append("    " + " ".join(f"o{k}[{i}] = {outs[8 * k + i]};" for i in range(8)))
     out.append("    (void)" + "; (void)".join(sgprs + vtemps) + ";")
@@ -293,26 +346,23 @@ def add_chain(h, a="a", b="b", cy="scy", upto=8, start=0):
 
 def gen_add(lat=False, acc=False):
     """Fast statement: the add chain with fix_test's compare placed as soon as h1 and h4 exist, then
-    m = carry | top and the fast fix-up (lat: fix_fast_lat).  Exact statement: the chain again and
-    fix_seq."""
+    m1 = carry | top (fix_m1) and, as a statement of its own, the fast fix-up (FIX_FAST).  Exact
+    statement: the chain again and fix_seq.  lat: the same block under the latency form's name."""
     h = [f"h{i}" for i in range(8)]
     fast = add_chain(h, upto=5) + [V("v_max_u32 %[vt3], %[h1], %[h4]"),
                                     V("v_cmp_eq_u32 %[srare], -1, %[vt3]", ["srare"])] + add_chain(h, start=5)
-    if lat:
-        fast += fix_fast_lat(h)
-    else:
-        fast += [V("v_cmp_gt_i32 %[stp], 0, %[h7]", ["stp"]), S("s_or_b64 %[sm], %[scy], %[stp]", ["sm"])] + fix_fast(h)
+    fast += fix_m1(h)
     lf, _ = schedule(fast)
     if acc:
         return emit_acc("fe_add_asm_lat_acc", ["fe_add_asm_lat's fast statement, the rare-edge test deferred into acc (emit_acc)."],
-                        [("fa", "a"), ("ga", "b")], h, ["vt1", "vt2", "vt3"], ["scy", "sk0", "sk2"],
-                        schedule(to_acc(fast))[0])
+                        [("fa", "a"), ("ga", "b")], h, ["vt1", "vt3"], ["scy"],
+                        schedule(to_acc(fast))[0], ADD_POST)
     ls, _ = schedule(add_chain(h) + fix_seq(h, h, "scy"))
     return emit_split("fe_add_asm" + ("_lat" if lat else ""), ["fe25519_add (curve25519_ops.cu:41-68) on limb halves: exact 257-bit sum, then",
                                      "one lossy \"- p\" when it carried out or is >= p (fast form unless a lane is",
                                      "on one of the fix-up's rare edges: fix_test)."],
                       [("fa", "a"), ("ga", "b")], h, ["vt1", "vt2", "vt3"],
-                      ["scy", "srare", "sk0", "sk2"] + ([] if lat else ["stp", "sm"]), lf, FIX_SGPRS + ["scy"], ls)
+                      ["scy", "srare"], lf, FIX_SGPRS + ["scy"], ls, ADD_POST, ["vt1", "vt3"])
 
 
 def gen_fold(lat=False, acc=False):
@@ -341,24 +391,20 @@ def gen_fold(lat=False, acc=False):
     fast = [V("v_max3_u32 %[vt3], %[x2], %[x4], %[x6]")] + plain[:5] + \
         [V(f"v_max3_u32 %[vt3], %[vt3], %[{h[1]}], %[{h[4]}]"),
          V("v_cmp_eq_u32 %[srare], -1, %[vt3]", ["srare"])] + plain[5:]
-    if lat:
-        fast += fix_fast_lat(h)
-    else:
-        fast += [V(f"v_cmp_gt_i32 %[stp], 0, %[{h[7]}]", ["stp"]),
-                 S(f"s_or_b64 %[sm], {cref('scy')}, %[stp]", ["sm"])] + fix_fast(h)
+    fast += fix_m1(h)
     lf, _ = schedule(fast)
     if acc:
         return emit_acc("fe_fold_asm_lat_acc", ["fe_fold_asm_lat's fast statement, the rare-edge test deferred into acc (emit_acc)."],
-                        [("ta", "a"), ("xa", "x")], h, ["vt1", "vt2", "vt3"], ["scy", "sk0", "sk2"],
-                        schedule(to_acc(fast))[0])
+                        [("ta", "a"), ("xa", "x")], h, ["vt1", "vt3"], ["scy"],
+                        schedule(to_acc(fast))[0], ADD_POST)
     ls, _ = schedule(exact + fix_seq(h, h, "scy"))
     return emit_split("fe_fold_asm" + ("_lat" if lat else ""), ["Fold of the exact 512-bit product (curve25519_ops.cu:114-145): t_lo as halves",
                                       "ta[0..7], x_i = lo64(19 t_{i+4}) as halves xa[0..7]; carry chain with the lossy",
                                       "carry cy_i = c_i & !(x_i == 2^64-1 & cy_{i-1}), then the fix-up.  The plain",
                                       "chain and the fast fix-up unless a lane is on a rare edge (wave-uniform test)."],
                       [("ta", "a"), ("xa", "x")], h, ["vt1", "vt2", "vt3"],
-                      ["scy", "srare", "sk0", "sk2"] + ([] if lat else ["stp", "sm"]), lf,
-                      FIX_SGPRS + ["scy", "sq1", "sq2", "sq3"], ls)
+                      ["scy", "srare"], lf,
+                      FIX_SGPRS + ["scy", "sq1", "sq2", "sq3"], ls, ADD_POST, ["vt1", "vt3"])
 
 
 def gen_sub():
@@ -373,11 +419,10 @@ def gen_sub():
     plain = [V("v_sub_co_u32 %[h0], %[scy], %[a0], %[b0]", ["scy"])]
     for i in range(1, 8):
         plain.append(V(f"v_subb_co_u32 %[h{i}], %[scy], %[a{i}], %[b{i}], %[scy]", ["scy"], ["scy"]))
-    fastp = [V("v_cndmask_b32 %[vt1], 0, 19, %[scy]", [], ["scy"]),
-             V("v_cndmask_b32 %[vt2], 0, %[c80], %[scy]", [], ["scy"]),
-             V("v_sub_co_u32 %[h0], %[sk0], %[h0], %[vt1]", ["sk0"]),
-             V("v_add_u32 %[h7], %[h7], %[vt2]"),
-             V("v_subb_co_u32 %[h1], %[sk0], %[h1], 0, %[sk0]", ["sk0"], ["sk0"])]
+    # the fast "+ p": mn = -m here, then SUBP_FAST (limb 0 -= 19 m as one 64-bit multiply-add, where
+    # the 32-bit form took two selects and a sub / sub-with-borrow pair; the same words: no link of
+    # the old form went past limb 0, the test having excluded t0 < 19)
+    fastp = [V("v_cndmask_b32 %[vt1], 0, -1, %[scy]", [], ["scy"])]
     exact = []
     for i in (1, 2, 3):   # g_i == 2^64-1
         exact.append(V(f"v_and_b32 %[vt1], %[b{2 * i}], %[b{2 * i + 1}]"))
@@ -420,8 +465,9 @@ def gen_sub():
     ls, _ = schedule(exact + exactp)
     return emit_split("fe_sub_asm", ["fe25519_sub (curve25519_ops.cu:71-90) on limb halves: lossy borrow chain, then the",
                                      "literal \"+ p\" pass on a final borrow (fast forms unless a lane is on a rare edge)."],
-                      [("fa", "a"), ("ga", "b")], t, ["vt1", "vt2", "vt3"], ["scy", "srare", "sk0"], lf,
-                      ["sk0", "sk1", "sk2", "sk3", "sd1", "sd2", "sd3", "scy", "sq1", "sq2", "sq3"], ls)
+                      [("fa", "a"), ("ga", "b")], t, ["vt1", "vt2", "vt3"], ["scy", "srare"], lf,
+                      ["sk0", "sk1", "sk2", "sk3", "sd1", "sd2", "sd3", "scy", "sq1", "sq2", "sq3"], ls,
+                      SUB_POST, ["vt1", "vt3"])
 
 
 def renamed(ins, names):
@@ -457,36 +503,8 @@ def gen_addsub(lat=False, acc=False):
          V("v_max3_u32 %[vt3], %[vt3], %[vt4], %[t2]"),
          V("v_max_u32 %[vt3], %[vt3], %[t4]"),
          V("v_cmp_eq_u32 %[srare], -1, %[vt3]", ["srare"])] + chains[10:]
-    if not lat:
-        pre += [V("v_cmp_gt_i32 %[stp], 0, %[h7]", ["stp"]), S("s_or_b64 %[sm], %[scy], %[stp]", ["sm"])]
-    fast = [V("v_cndmask_b32 %[vt1], 0, 19, %[sm]", [], ["sm"]),
-            V("v_cndmask_b32 %[vt4], 0, 19, %[sby]", [], ["sby"]),
-            V("v_cndmask_b32 %[vt2], 0, %[c80], %[sm]", [], ["sm"]),
-            V("v_cndmask_b32 %[vt5], 0, %[c80], %[sby]", [], ["sby"]),
-            V("v_add_co_u32 %[h0], %[sk0], %[h0], %[vt1]", ["sk0"]),
-            V("v_sub_co_u32 %[t0], %[sk1], %[t0], %[vt4]", ["sk1"]),
-            V("v_addc_co_u32 %[h4], %[sk2], %[h4], 0, %[sm]", ["sk2"], ["sm"]),
-            V("v_add_u32 %[h7], %[h7], %[vt2]"),
-            V("v_add_u32 %[t7], %[t7], %[vt5]"),
-            V("v_addc_co_u32 %[h1], %[sk0], %[h1], 0, %[sk0]", ["sk0"], ["sk0"]),
-            V("v_subb_co_u32 %[t1], %[sk1], %[t1], 0, %[sk1]", ["sk1"], ["sk1"]),
-            V("v_addc_co_u32 %[h5], %[sk2], %[h5], 0, %[sk2]", ["sk2"], ["sk2"])]
-    if lat:   # add's m = carry | top as a VALU mask (fix_fast_lat), sub's "+ p" as above, interleaved
-        fast = [V("v_ashrrev_i32 %[vt2], 31, %[h7]"),
-                V("v_cndmask_b32 %[vt4], 0, 19, %[sby]", [], ["sby"]),
-                V("v_cndmask_b32 %[vt2], %[vt2], -1, %[scy]", [], ["scy"]),
-                V("v_cndmask_b32 %[vt5], 0, %[c80], %[sby]", [], ["sby"]),
-                V("v_and_b32 %[vt1], 19, %[vt2]"),
-                V("v_lshrrev_b32 %[vt3], 31, %[vt2]"),
-                V("v_and_b32 %[vt2], %[c80], %[vt2]"),
-                V("v_add_co_u32 %[h0], %[sk0], %[h0], %[vt1]", ["sk0"]),
-                V("v_sub_co_u32 %[t0], %[sk1], %[t0], %[vt4]", ["sk1"]),
-                V("v_add_co_u32 %[h4], %[sk2], %[h4], %[vt3]", ["sk2"]),
-                V("v_add_u32 %[h7], %[h7], %[vt2]"),
-                V("v_add_u32 %[t7], %[t7], %[vt5]"),
-                V("v_addc_co_u32 %[h1], %[sk0], %[h1], 0, %[sk0]", ["sk0"], ["sk0"]),
-                V("v_subb_co_u32 %[t1], %[sk1], %[t1], 0, %[sk1]", ["sk1"], ["sk1"]),
-                V("v_addc_co_u32 %[h5], %[sk2], %[h5], 0, %[sk2]", ["sk2"], ["sk2"])]
+    # add's m1 (fix_m1) and sub's mn = -m, the add side first: its carry is one link older
+    fast = fix_m1(h) + [V("v_cndmask_b32 %[vt4], 0, -1, %[sby]", [], ["sby"])]
     add_exact = [V("v_add_co_u32 %[h0], %[scy], %[a0], %[b0]", ["scy"])]
     for i in range(1, 8):
         add_exact.append(V(f"v_addc_co_u32 %[h{i}], %[scy], %[a{i}], %[b{i}], %[scy]", ["scy"], ["scy"]))
@@ -526,24 +544,26 @@ def gen_addsub(lat=False, acc=False):
     if acc:
         return emit_acc("fe_addsub_asm_lat_acc", ["fe_addsub_asm_lat's fast statement, the rare-edge test deferred into acc (emit_acc)."],
                         [("fa", "a"), ("ga", "b")], h + [f"t{i}" for i in range(8)],
-                        ["vt1", "vt2", "vt3", "vt4", "vt5"], ["scy", "sby", "sk0", "sk1", "sk2"],
-                        schedule(to_acc(pre + fast))[0])
+                        ["vt1", "vt3", "vt4"], ["scy", "sby"],
+                        schedule(to_acc(pre + fast))[0], ADDSUB_POST)
     ls, _ = schedule(add_exact + sub_exact)
     return emit_split("fe_addsub_asm" + ("_lat" if lat else ""), ["fe_add(a, b) and fe_sub(a, b) in one block (curve25519_ops.cu:41-90): the two carry",
                                         "chains interleaved, one rare-edge test for both (tools/gen_field_asm.py gen_addsub)."],
                       [("fa", "a"), ("ga", "b")], h + [f"t{i}" for i in range(8)], ["vt1", "vt2", "vt3", "vt4", "vt5"],
-                      ["scy", "sby", "srare", "sk0", "sk1", "sk2"] + ([] if lat else ["stp", "sm"]), lf,
-                      FIX_SGPRS + ["scy", "sby", "sq1", "sq2", "sq3"], ls)
+                      ["scy", "sby", "srare"], lf,
+                      FIX_SGPRS + ["scy", "sby", "sq1", "sq2", "sq3"], ls, ADDSUB_POST, ["vt1", "vt3", "vt4"])
 
 
 def gen_canon():
     """host fe25519_tobytes' conditional "- p" (curve25519_ops.cu:220-251) = device fe_mul_one:
-    the fix-up with no carry, in place."""
+    the fix-up with no carry, in place.  The exact path forms its 0x80000000 itself (vt4), so the
+    common path of fe_mul_one has no constant to materialise."""
     h = [f"h{i}" for i in range(8)]
-    lines = two_way(fix_test(h, "0"), fix_fast(h), fix_seq(h, h, "0"))
+    lines = two_way(fix_test(h), fix_fast32(h),
+                    [V("v_bfrev_b32 %[vt4], 1")] + renamed(fix_seq(h, h, "0"), {"c80": "vt4"}))
     return emit("fe_canon_asm", ["Canonicalising \"- p\" of fe25519_tobytes (curve25519_ops.cu:220-251), in place:",
                                  "h >= p ? lossy - p : h (fast form unless a lane is on a rare edge)."],
-                [("ha", "h")], [], h, ["vt1", "vt2", "vt3"], FIX_SGPRS + ["srare"], lines, inout=True)
+                [("ha", "h")], [], h, ["vt1", "vt2", "vt3", "vt4"], FIX_SGPRS + ["srare"], lines, inout=True, c80=False)
 
 
 def gen_q4_sum():
@@ -618,10 +638,10 @@ def main(path=OUT):
     out = ["// GENERATED by tools/gen_field_asm.py -- do not edit by hand.",
            "// gfx950 inline-asm fe25519 add and product fold: the same bits as the C forms in fe25519_dev.h.",
            "#pragma once", "#include <stdint.h>", "namespace bp {"]
-    out += gen_add() + [""] + gen_sub() + [""] + gen_fold() + [""] + gen_canon() + [""] + gen_addsub() + [""] + \
+    out += emit_fixups() + [""] + gen_add() + [""] + gen_sub() + [""] + gen_fold() + [""] + gen_canon() + [""] + gen_addsub() + [""] + \
         gen_q4_sum() + [""]
-    out += ["// Latency forms (the 16-lane row step, one wave per SIMD): the same blocks with m = carry | top",
-            "// computed in VALU (fix_fast_lat) instead of a compare + SALU OR; same bits."]
+    out += ["// Latency forms (the 16-lane row step, one wave per SIMD): since the fix-up forms m in VALU for every",
+            "// form (fix_m1) these are the blocks above again, kept under the names their callers select by."]
     out += gen_add(lat=True) + [""] + gen_fold(lat=True) + [""] + gen_addsub(lat=True) + [""]
     out += ["// The row step's fast statements with the rare-edge test deferred (emit_acc; ge25519_quad.h sm_row)."]
     out += gen_add(lat=True, acc=True) + [""] + gen_fold(lat=True, acc=True) + [""] + gen_addsub(lat=True, acc=True)
