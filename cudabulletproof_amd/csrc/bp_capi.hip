@@ -19,7 +19,7 @@
 #include <thread>
 
 #include "../../include/cudabulletproof_hip.h"
-#include "bp_kernels.h"
+#include "bp_tick_plan.h"
 #include "ge25519_dev.h"
 
 static_assert(sizeof(fe25519) == 32, "fe25519 layout");
@@ -323,20 +323,6 @@ bp::BatchView view_of(const hipbp_proof_batch* b) {
     return v;
 }
 
-// The verify pipeline: a ring of D batch slots.  Every tick is ONE k_terms launch over all
-// in-flight batches, each at its own stage; within a batch the reference's order is kept
-// exactly, across batches nothing depends on anything.  Stages of a batch with L fold rounds
-// (Pipeline::stages):
-//   0: RK_PREP (challenges, MSM scalars, round challenges)
-//   1: RK_STAGE0 (both MSMs' point terms, fold round 0, t*h, c*Q [, the 7 polynomial terms])
-//   2: RK_TREE (MSM trees of n > LANE_TREE_MAX points) [, RK_POLY]   r+1 (1 <= r < L): RK_ROUND r
-//   FT = L+1 (1 when L = 0): RK_FINAL_TERMS           mode 2, max(3, FT): RK_M3
-//   min(3, FIN - 1): RK_LTREE (the trees of n <= LANE_TREE_MAX MSMs, one lane per proof)
-//   FIN = 1 + the last of those: RK_FINAL (P, check point, accept)
-// Ticks too small to fill the SIMDs (a drain's last ticks, a one-proof verify) run in the lane-quad
-// form (QUAD_MAX_ITEMS below).
-// A round-r item forms its own input point G'/H' from two round r-1 terms (each folded point
-// has exactly one consumer), so no launch of its own is needed for the fold combinations.
 // A generator set (hipbp_gens_create): a device snapshot of G[n] | H[n] | h | g and, optionally,
 // their fixed-base prefix tables (bp::launch_prefix_tables, same base order).
 struct Gens {
@@ -355,7 +341,7 @@ struct Gens {
     }
 };
 
-// Drain-tick thresholds (Pipeline::push): ticks with at most this many scalar-multiplication items
+// Drain-tick thresholds (bp::plan_tick): ticks with at most this many scalar-multiplication items
 // run them on lane quads, up to PAIR_MAX_ITEMS on lane pairs.  The cost model (tools/ubench_issue.hip
 // with -DLAT: one wave alone issues one instruction per ~9 cycles, the SIMD one per ~4.4): a tick
 // lasts about (instructions per wave) x max(9, 4.4 w) cycles for w waves per SIMD, counting the other
@@ -369,120 +355,68 @@ constexpr unsigned long long ROW_MAX_ITEMS = 2048;
 constexpr unsigned long long QUAD_MAX_ITEMS = 16384;
 constexpr unsigned long long PAIR_MAX_ITEMS = 32768;
 
+// The verify pipeline: a ring of D batch slots, one tick per push (the stage table, the tick's
+// layout and its form: bp_tick_plan.h).
 struct Pipeline {
     Engine* e = nullptr;
     hipStream_t s = nullptr;
-    int n = 0, Lr = 0, D = 0;
-    size_t maxB = 0;
+    int n = 0, D = 0;
     int range_mode = 1;   // 0 inner product only, 1 cuda_range_proof_verify, 2 range_proof_verify
     const bp::ge *G = nullptr, *H = nullptr, *g = nullptr, *h = nullptr;
+    // a slot's device buffers: the verify workspace (bp::VerifyWs), its mode-2 part, the lane orders
+    enum { B_SG, B_SH, B_SC, B_U, B_UINV, B_IPOK, B_MSM_PTS, B_MSM_PART, B_TERMS, B_FOLD0, B_FOLD1, B_FIN, B_PIN,
+           B_PSC, B_PTERM, B_LR, B_CHAL, B_M3, B_RFLAGS, B_PERM, B_PBASE, B_COUNT };
     struct Slot {
-        Buf b[24];
+        Buf b[B_COUNT];
         bp::SlotDev dev{};
-        bool active = false;
-        int stage = 0;
-        size_t B = 0;
         hipEvent_t copied = nullptr;
     };
     std::vector<Slot> slots;
+    bp::PlanSlot ring[bp::MAX_DEPTH];   // the slots' planning state (active, stage, B, L, defer)
     bp::SlotDev* slots_dev = nullptr;   // device copies [D]
     bp::SlotDev* host_dev = nullptr;    // pinned staging [D]
     int head = 0;
-
-    struct Stages {
-        int ft, m3, fin;
-    };
-    Stages stages(int L) const {
-        Stages g;
-        g.ft = L > 0 ? L + 1 : 1;
-        g.m3 = range_mode == 2 ? (g.ft > 3 ? g.ft : 3) : -1;
-        int last = g.ft;
-        if (range_mode && last < 2) last = 2;       // the MSM trees (RK_TREE blocks when n > LANE_TREE_MAX)
-        if (g.m3 > last) last = g.m3;
-        g.fin = last + 1;
-        return g;
-    }
-    // Layout switches (A/B runs in round 1; defaults = the measured best on MI355X,
-    // 138.7K verifies/s lane trees + chains last vs 137.9K block trees, 130.6K lane trees + chains
-    // first): HIPBP_LANE_TREE_MAX (lane trees for n <= it), HIPBP_CHAINS_FIRST (per-proof chain
-    // regions at the start of the grid instead of the end).
-    bool lane_tree = false, chains_first = false;
-    // Split stage 0 ("deferred MSM terms", hipbp_pipeline_defer_msm / HIPBP_DEFER_MSM=1): a batch
-    // pushed with it on runs only fold round 0 (+ the polynomial terms) in its stage-0 tick; its
-    // MSM terms, t*h and c*Q (read only by the lane trees and the final assembly) run as RK_MSMT
-    // chunks inside its fold-round ticks (stages 2 .. L), whose items shrink round by round, and
-    // the lane trees move to the stage after the last chunk (the final-terms tick).  For a finite batch
-    // (configs[4]'s shards) the rounds that would run half empty before the latency-bound last
-    // ticks carry the MSM work instead.  Needs the lane trees (n <= 64) and L >= 2.
+    // Layout switches (defaults = the measured best on MI355X): HIPBP_LANE_TREE_MAX (lane trees for
+    // n <= it; 138.7K verifies/s vs 137.9K block trees); the tick forms: HIPBP_QUAD forces lanes (0) /
+    // quads (1) / pairs (2) / rows (3) on every tick, HIPBP_ROW_MAX_ITEMS / HIPBP_QUAD_MAX_ITEMS /
+    // HIPBP_PAIR_MAX_ITEMS move the size bounds; HIPBP_LANE_SORT (bp::lane_sort_sets' mask, 0: off)
+    bp::PlanConfig cfg;
+    // Split stage 0 ("deferred MSM terms", hipbp_pipeline_defer_msm / HIPBP_DEFER_MSM=1) for the
+    // batches pushed from now on, where bp::batch_defers allows it (lane trees, L >= 2)
     bool defer_msm = false;
-    // drain-tick forms (push): HIPBP_QUAD forces lanes (0) / quads (1) / pairs (2) on every tick
-    // (-1: by size), HIPBP_QUAD_MAX_ITEMS / HIPBP_PAIR_MAX_ITEMS move the size bounds
-    int quad_force = -1;
-    unsigned long long row_max = ROW_MAX_ITEMS, quad_max = QUAD_MAX_ITEMS, pair_max = PAIR_MAX_ITEMS;
-    // Lane sort (bp::launch_lane_sort): per-lane-scalar items in chain-length order, for batches
-    // of at least LANE_SORT_MIN proofs (HIPBP_LANE_SORT=0 turns it off, for A/B runs).
-    static constexpr size_t LANE_SORT_MIN = 64;
-    bool lane_sort = true;
-    int lane_sort_mask = 7;   // bit 0 stage 0, bit 1 rounds, bit 2 final terms, bit 3 shortest first
     Buf sort_bins, sort_offs;
     bp::LaneSortPlan plan{};
-    // HIPBP_SORT_STREAM=1: the lane sort's three small launches on a high-priority stream of their
-    // own (between two events), so a concurrent pipeline's big tick cannot starve them of workgroup
-    // slots (a 4096-proof shard batch's sort once waited 7 ms behind the other pipeline's stage 0).
-    // Off by default since the sort runs in 256-thread blocks, which fit beside a running tick:
-    // then 172.5 vs 171.5 K (shard) and 190.4 vs 189.5 K (headline) verifies/s without it.
-    hipStream_t sort_s = nullptr;
-    hipEvent_t ev_tick = nullptr, ev_sorted = nullptr;
     // fixed-base prefix tables of G, H, h, g (hipbp_pipeline_prefix_tables: ptab, owned; or a
     // generator set's, hipbp_pipeline_use_gens: ext_tab, borrowed); pbits = 0: none
     Buf ptab;
     const bp::ge* ext_tab = nullptr;
     int pbits = 0;
     const bp::ge* tables() const { return ext_tab ? ext_tab : ptab.as<bp::ge>(); }
-    hipError_t init(Engine* eng, hipStream_t st, size_t mb, int nn, int range) {
-        e = eng; s = st; maxB = mb; n = nn; range_mode = range;
+    hipError_t init(Engine* eng, hipStream_t st, int nn, int range) {
+        e = eng; s = st; n = nn; range_mode = range;
+        cfg.n = n; cfg.range_mode = range;
+        // the knobs, read once per pipeline (push runs on the issue path)
         const char* ls = getenv("HIPBP_LANE_SORT");
-        lane_sort_mask = ls ? atoi(ls) : 7;
-        lane_sort = (lane_sort_mask & 7) != 0;
+        cfg.lane_sort_mask = ls ? atoi(ls) : 7;
         const char* lt = getenv("HIPBP_LANE_TREE_MAX");
-        lane_tree = n <= (lt ? atoi(lt) : bp::LANE_TREE_MAX);
-        const char* cf = getenv("HIPBP_CHAINS_FIRST");
-        chains_first = cf ? atoi(cf) != 0 : false;
-        // drain-tick form knobs, read once per pipeline (push runs on the issue path)
+        cfg.lane_tree = n <= (lt ? atoi(lt) : bp::LANE_TREE_MAX);
         const char* qe = getenv("HIPBP_QUAD");
+        cfg.quad_force = qe ? (atoi(qe) == 1 ? 4 : atoi(qe) == 2 ? 2 : atoi(qe) == 3 ? 16 : 1) : -1;
+        const char* rm = getenv("HIPBP_ROW_MAX_ITEMS");
         const char* qm = getenv("HIPBP_QUAD_MAX_ITEMS");
         const char* pm = getenv("HIPBP_PAIR_MAX_ITEMS");
-        quad_force = qe ? (atoi(qe) == 1 ? 4 : atoi(qe) == 2 ? 2 : atoi(qe) == 3 ? 16 : 1) : -1;
-        const char* rm = getenv("HIPBP_ROW_MAX_ITEMS");
-        row_max = rm ? strtoull(rm, nullptr, 10) : ROW_MAX_ITEMS;
-        quad_max = qm ? strtoull(qm, nullptr, 10) : QUAD_MAX_ITEMS;
-        pair_max = pm ? strtoull(pm, nullptr, 10) : PAIR_MAX_ITEMS;
+        cfg.row_max = rm ? strtoull(rm, nullptr, 10) : ROW_MAX_ITEMS;
+        cfg.quad_max = qm ? strtoull(qm, nullptr, 10) : QUAD_MAX_ITEMS;
+        cfg.pair_max = pm ? strtoull(pm, nullptr, 10) : PAIR_MAX_ITEMS;
         const char* dm = getenv("HIPBP_DEFER_MSM");
         defer_msm = dm && atoi(dm) != 0;
-        if (const char* sp = getenv("HIPBP_DEFER_SPAN")) {
-            int a = 2, b = 1, c = 0;
-            if (sscanf(sp, "%d:%d:%d", &a, &b, &c) >= 1 && a >= 2) {
-                defer_first = a;
-                defer_last_off = b < 0 ? 0 : b;
-                defer_weight = c != 0;
-            }
-        }
-        Lr = log2i((size_t)n);
-        D = stages(Lr).fin + 1;   // batches with fewer rounds finish earlier
+        D = bp::pipeline_depth(cfg);
         slots.resize(D);
         hipError_t r;
         if ((r = hipMalloc(&slots_dev, D * sizeof(bp::SlotDev))) != hipSuccess) return r;
         if ((r = hipHostMalloc(&host_dev, D * sizeof(bp::SlotDev))) != hipSuccess) return r;
         for (auto& sl : slots)
             if ((r = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming)) != hipSuccess) return r;
-        const char* ss = getenv("HIPBP_SORT_STREAM");
-        if (ss && atoi(ss) != 0) {
-            int lo_pr = 0, hi_pr = 0;
-            if ((r = hipDeviceGetStreamPriorityRange(&lo_pr, &hi_pr)) != hipSuccess) return r;
-            if ((r = hipStreamCreateWithPriority(&sort_s, hipStreamNonBlocking, hi_pr)) != hipSuccess) return r;
-            if ((r = hipEventCreateWithFlags(&ev_tick, hipEventDisableTiming)) != hipSuccess) return r;
-            if ((r = hipEventCreateWithFlags(&ev_sorted, hipEventDisableTiming)) != hipSuccess) return r;
-        }
         return hipSuccess;
     }
     void release() {
@@ -493,121 +427,75 @@ struct Pipeline {
         }
         if (slots_dev) (void)hipFree(slots_dev);
         if (host_dev) (void)hipHostFree(host_dev);
-        if (sort_s) (void)hipStreamSynchronize(sort_s);
-        if (sort_s) (void)hipStreamDestroy(sort_s);
-        if (ev_tick) (void)hipEventDestroy(ev_tick);
-        if (ev_sorted) (void)hipEventDestroy(ev_sorted);
         if (sort_bins.p) (void)hipFree(sort_bins.p);
         if (sort_offs.p) (void)hipFree(sort_offs.p);
         if (ptab.p) (void)hipFree(ptab.p);
     }
-    // The batch's per-lane item sets (stage 0's per-lane part, the rounds whose scalar runs are
-    // shorter than a wave, the final terms), their lane-order buffers and the sort plan.
+    // The batch's lane-order buffers and sort plan (its per-lane item sets: bp::lane_sort_sets).
     hipError_t plan_sort(Slot& sl, int idx) {
         plan = bp::LaneSortPlan{};
         bp::SlotDev& d = sl.dev;
         d.perm0 = nullptr;
         for (auto& q : d.permr) q = nullptr;
         d.perm_ft = nullptr;
-        const unsigned long long B = d.bv.B;
-        const int L = d.bv.L_len;
-        if (!lane_sort || B < LANE_SORT_MIN) return hipSuccess;
-        struct S { int kind, r; unsigned long long items; };
-        S sets[bp::LANE_SORT_SETS];
-        int cnt = 0;
-        const bp::Stage0Lanes z = bp::stage0_lanes(B, n, L, range_mode);
-        for (int c = 0; c < 4; c++)   // one set per class, contiguous in perm0 (stage0_item)
-            if (z.size[c] && (lane_sort_mask & 1)) sets[cnt++] = {bp::SS_STAGE0, c, z.size[c]};
-        for (int r = 1; r < L; r++)
-            if (bp::round_per_lane(n, r) && (lane_sort_mask & 2))
-                sets[cnt++] = {bp::SS_ROUND, r, B * 4 * (unsigned long long)(n >> (r + 1))};
-        if (lane_sort_mask & 4) sets[cnt++] = {bp::SS_FT, 0, B * 2};
-        if (!cnt) return hipSuccess;
-        plan.longest_first = (lane_sort_mask & 8) ? 0 : 1;
-        unsigned long long total = 0;
-        for (int k = 0; k < cnt; k++) total += sets[k].items;
-        if (total > 0xFFFFFFFFull) return hipSuccess;
+        const bp::SortSets ss = bp::lane_sort_sets(cfg, d.bv.B, d.bv.L_len);
+        if (!ss.count) return hipSuccess;
+        plan.longest_first = (cfg.lane_sort_mask & 8) ? 0 : 1;
         hipError_t r;
-        if ((r = sl.b[20].need(total * sizeof(uint32_t))) != hipSuccess) return r;
+        if ((r = sl.b[B_PERM].need(ss.total * sizeof(uint32_t))) != hipSuccess) return r;
         const size_t nb = (size_t)bp::LANE_SORT_SETS * bp::MSM_BINS * sizeof(unsigned);
         if (!sort_bins.p) {
             if ((r = sort_bins.need(nb)) != hipSuccess) return r;
             if ((r = hipMemsetAsync(sort_bins.p, 0, nb, s)) != hipSuccess) return r;
             if ((r = sort_offs.need(nb)) != hipSuccess) return r;
         }
-        uint32_t* base = sl.b[20].as<uint32_t>();
-        unsigned blk = 0;
-        for (int k = 0; k < cnt; k++) {
+        uint32_t* base = sl.b[B_PERM].as<uint32_t>();
+        for (int k = 0; k < ss.count; k++) {
             bp::LaneSortPlan::Set& st = plan.set[k];
-            st.kind = sets[k].kind; st.r = sets[k].r; st.items = sets[k].items; st.perm = base; st.block0 = blk;
+            st.kind = ss.set[k].kind; st.r = ss.set[k].r; st.items = ss.set[k].items; st.perm = base;
+            st.block0 = ss.set[k].block0;
             if (st.kind == bp::SS_STAGE0 && !d.perm0) d.perm0 = base;
             else if (st.kind == bp::SS_ROUND) d.permr[st.r] = base;
             else d.perm_ft = base;
-            base += sets[k].items;
-            blk += (unsigned)((sets[k].items + bp::LANE_SORT_BLOCK - 1) / bp::LANE_SORT_BLOCK);
+            base += st.items;
         }
-        plan.count = cnt;
-        plan.blocks = blk;
+        plan.count = ss.count;
+        plan.blocks = ss.blocks;
         plan.slot = slots_dev + idx;
         return hipSuccess;
     }
     bool busy() const {
-        for (auto& sl : slots) if (sl.active) return true;
+        for (int k = 0; k < D; k++) if (ring[k].active) return true;
         return false;
-    }
-    // A split batch adds one RK_MSMT region to each of its stages 2 .. L: in steady state a tick then
-    // holds up to 2 L + 5 regions (RK_STAGE0, L - 1 RK_ROUND + L - 1 RK_MSMT, RK_FINAL_TERMS, RK_M3,
-    // RK_FINAL, RK_LTREE, RK_POLY, RK_PREP), which must fit the kernel's region list (n <= 512 when
-    // HIPBP_LANE_TREE_MAX raises the lane-tree limit; the default limit is n <= 64, 17 regions).
-    bool defer_ok() const { return range_mode != 0 && lane_tree && Lr >= 2 && 2 * Lr + 5 <= bp::MAX_REGIONS; }
-    // a split batch's MSM-term chunks: stages defer_first .. msm_last(L), wave-aligned lane ranges
-    // (HIPBP_DEFER_SPAN = "first:last_off:weight" for A/B runs: chunks at stages first .. L - last_off
-    // (at least first), weight 0 equal chunks, 1 chunk k weighted 2^k: later, emptier rounds get more)
-    // default 2:0:0 (r04k, 8192-proof shard: 180.7 / 181.2 K vs 178.4 / 178.2 K with 2:1:0)
-    int defer_first = 2, defer_last_off = 0, defer_weight = 0;
-    int msm_last(int L) const { return L - defer_last_off > defer_first ? L - defer_last_off : defer_first; }
-    void msm_chunk(unsigned long long total, int L, int st, unsigned long long& lo, unsigned long long& hi) const {
-        const int m = msm_last(L) - defer_first + 1, k = st - defer_first;   // m chunks, this is chunk k
-        auto cut = [&](int j) -> unsigned long long {   // lanes before chunk j
-            if (j >= m) return total;
-            const unsigned long long num = defer_weight ? (1ull << j) - 1 : (unsigned long long)j;
-            const unsigned long long den = defer_weight ? (1ull << m) - 1 : (unsigned long long)m;
-            return (total / 64 * num / den) * 64;
-        };
-        lo = cut(k);
-        hi = cut(k + 1);
-    }
-    int ltree_stage(const Slot& sl, const Stages& g) const {
-        return sl.dev.defer ? msm_last(sl.dev.bv.L_len) + 1 : std::min(3, g.fin - 1);
     }
     hipError_t carve(Slot& sl, size_t B, size_t Lb) {
         hipError_t r;
         size_t Lc = Lb ? Lb : 1;
-        size_t sz[14] = {B * 32, B * n * 32, B * 4 * 32, B * Lc * 32, B * Lc * 32, B, B * 2 * n * 128, B * 2 * 128,
-                         B * 4 * 128, B * 2 * n * 128, B * 2 * n * 128, 0, B * 2 * 128, B * 128};
-        for (int i = 0; i < 14; i++)
+        const size_t sz[B_PSC] = {B * 32, B * n * 32, B * 4 * 32, B * Lc * 32, B * Lc * 32, B, B * 2 * n * 128,
+                                  B * 2 * 128, B * 4 * 128, B * 2 * n * 128, B * 2 * n * 128, B * 2 * 128, B * 128};
+        for (int i = 0; i < B_PSC; i++)
             if ((r = sl.b[i].need(sz[i])) != hipSuccess) return r;
         bp::VerifyWs& w = sl.dev.ws;
-        w.sG = sl.b[0].as<bp::fe>(); w.sH = sl.b[1].as<bp::fe>(); w.sc = sl.b[2].as<bp::fe>();
-        w.u = sl.b[3].as<bp::fe>(); w.uinv = sl.b[4].as<bp::fe>(); w.ipok = sl.b[5].as<uint8_t>();
-        w.msm_pts = sl.b[6].as<bp::ge>(); w.msm_part = sl.b[7].as<bp::ge>(); w.terms = sl.b[8].as<bp::ge>();
-        w.fold[0] = sl.b[9].as<bp::ge>(); w.fold[1] = sl.b[10].as<bp::ge>();
-        w.fin = sl.b[12].as<bp::ge>(); w.Pin = sl.b[13].as<bp::ge>();
+        w.sG = sl.b[B_SG].as<bp::fe>(); w.sH = sl.b[B_SH].as<bp::fe>(); w.sc = sl.b[B_SC].as<bp::fe>();
+        w.u = sl.b[B_U].as<bp::fe>(); w.uinv = sl.b[B_UINV].as<bp::fe>(); w.ipok = sl.b[B_IPOK].as<uint8_t>();
+        w.msm_pts = sl.b[B_MSM_PTS].as<bp::ge>(); w.msm_part = sl.b[B_MSM_PART].as<bp::ge>();
+        w.terms = sl.b[B_TERMS].as<bp::ge>();
+        w.fold[0] = sl.b[B_FOLD0].as<bp::ge>(); w.fold[1] = sl.b[B_FOLD1].as<bp::ge>();
+        w.fin = sl.b[B_FIN].as<bp::ge>(); w.Pin = sl.b[B_PIN].as<bp::ge>();
         if (range_mode == 2) {
-            size_t sz2[6] = {B * 8 * 32, B * 8 * 128, B * 2 * 128, B * 32, B * 2 * 128, B};
+            const size_t sz2[6] = {B * 8 * 32, B * 8 * 128, B * 2 * 128, B * 32, B * 2 * 128, B};
             for (int i = 0; i < 6; i++)
-                if ((r = sl.b[14 + i].need(sz2[i])) != hipSuccess) return r;
-            if ((r = sl.b[21].need(B * 3 * 128)) != hipSuccess) return r;
-            w.psc = sl.b[14].as<bp::fe>(); w.pterm = sl.b[15].as<bp::ge>(); w.lr = sl.b[16].as<bp::ge>();
-            w.chal = sl.b[17].as<bp::fe>(); w.m3 = sl.b[18].as<bp::ge>(); w.rflags = sl.b[19].as<uint8_t>();
-            w.pbase = sl.b[21].as<bp::ge>();
+                if ((r = sl.b[B_PSC + i].need(sz2[i])) != hipSuccess) return r;
+            if ((r = sl.b[B_PBASE].need(B * 3 * 128)) != hipSuccess) return r;
+            w.psc = sl.b[B_PSC].as<bp::fe>(); w.pterm = sl.b[B_PTERM].as<bp::ge>(); w.lr = sl.b[B_LR].as<bp::ge>();
+            w.chal = sl.b[B_CHAL].as<bp::fe>(); w.m3 = sl.b[B_M3].as<bp::ge>(); w.rflags = sl.b[B_RFLAGS].as<uint8_t>();
+            w.pbase = sl.b[B_PBASE].as<bp::ge>();
         } else {
             w.psc = nullptr; w.pterm = nullptr; w.lr = nullptr; w.chal = nullptr; w.m3 = nullptr; w.rflags = nullptr;
             w.pbase = nullptr;
         }
         return hipSuccess;
     }
-
     // One tick; `b` may be null (drain).  Outputs of `b` are written when it completes.
     int push(const hipbp_proof_batch* b, const ge25519* P_in, uint8_t* ok, ge25519* P_out, ge25519* chk,
              uint8_t* flags_out = nullptr, ge25519* poly_out = nullptr) {
@@ -618,7 +506,7 @@ struct Pipeline {
             int rc = check_batch(b, range_mode);
             if (rc != HIPBP_OK) return rc;
             if ((int)b->n != n) { g_err = "batch n differs from the pipeline's"; return HIPBP_ERR_ARG; }
-            if (nw.active) { g_err = "pipeline slot busy (internal)"; return HIPBP_ERR_ARG; }
+            if (ring[head].active) { g_err = "pipeline slot busy (internal)"; return HIPBP_ERR_ARG; }
             BP_RET_ON(carve(nw, b->count, b->L_len));
             nw.dev.bv = view_of(b);
             nw.dev.ok = ok;
@@ -627,12 +515,10 @@ struct Pipeline {
             nw.dev.flags_out = flags_out;
             nw.dev.poly_out = (bp::ge*)poly_out;
             nw.dev.range_mode = range_mode;
-            nw.dev.lane_tree = lane_tree ? 1 : 0;
+            nw.dev.lane_tree = cfg.lane_tree ? 1 : 0;
             nw.dev.ptab = pbits ? tables() : nullptr;
             nw.dev.pbits = pbits;
-            // (the lane trees must land at least one tick before the final assembly)
-            nw.dev.defer = (defer_msm && defer_ok() && (int)b->L_len >= 2 &&
-                            msm_last((int)b->L_len) + 1 < stages((int)b->L_len).fin) ? 1 : 0;
+            nw.dev.defer = (defer_msm && bp::batch_defers(cfg, (int)b->L_len)) ? 1 : 0;
             BP_RET_ON(plan_sort(nw, head));
             BP_RET_ON(hipEventSynchronize(nw.copied));   // staging slot free again
             host_dev[head] = nw.dev;
@@ -640,112 +526,21 @@ struct Pipeline {
             BP_RET_ON(hipEventRecord(nw.copied, s));
             if (!range_mode)
                 BP_RET_ON(hipMemcpyAsync(nw.dev.ws.Pin, P_in, b->count * sizeof(ge25519), hipMemcpyDeviceToDevice, s));
-            nw.active = true;
-            nw.stage = 0;
-            nw.B = b->count;
+            ring[head] = bp::PlanSlot{true, 0, b->count, (int)b->L_len, nw.dev.defer};
         }
-        bp::RegionList tr{};
-        bool overflow = false;
-        auto add = [&overflow](bp::RegionList& rl, int kind, int slot, int r, unsigned long long items, unsigned align) {
-            if (!items) return;
-            if (rl.count == bp::MAX_REGIONS) { overflow = true; return; }
-            bp::Region& g = rl.reg[rl.count++];
-            g.kind = kind; g.slot = slot; g.r = r; g.begin = rl.total; g.items = items;
-            rl.total += (items + align - 1) & ~(unsigned long long)(align - 1);   // wave / block aligned
-        };
-        // pass 0: the (block-aligned) tree region, which must start the list; pass 2: the scalar
-        // multiplications; the per-proof chains (final assembly incl. lane trees, polynomial
-        // sides, challenges) in pass 3 by default (measured faster than pass 1, the grid start)
-        const int chain_pass = chains_first ? 1 : 3;
-        for (int pass = 0; pass < 4; pass++) {
-            for (int k = 0; k < D; k++) {
-                int idx = (head - k + D) % D;   // newest first
-                Slot& sl = slots[idx];
-                if (!sl.active) continue;
-                unsigned long long B = sl.dev.bv.B;
-                int L = sl.dev.bv.L_len, st = sl.stage;
-                const Stages g = stages(L);
-                if (pass == 0) {
-                    if (st == 2 && range_mode && !lane_tree) add(tr, bp::RK_TREE, idx, 0, B * 2 * n, 256);
-                } else if (pass == chain_pass) {
-                    if (st == g.fin) add(tr, bp::RK_FINAL, idx, 0, B, 64);
-                    // the lane MSM trees need only stage 0's terms: a few ticks before the final one,
-                    // so a drain's last tick is the short P / check-point assembly alone
-                    if (range_mode && lane_tree && st == ltree_stage(sl, g)) {
-                        add(tr, bp::RK_LTREE, idx, 0, B, 64);
-                    }
-                    if (st == 2 && range_mode == 2) add(tr, bp::RK_POLY, idx, 0, B, 64);
-                    if (st == 0) add(tr, bp::RK_PREP, idx, 0, range_mode ? 2 * B : B, 64);
-                } else if (pass == 2) {
-                    if (st == 1) {
-                        add(tr, bp::RK_STAGE0, idx, 0,
-                            bp::stage0_lanes(B, n, L, range_mode, sl.dev.defer ? bp::S0_CRIT : bp::S0_ALL).total, 64);
-                    }
-                    if (st >= 2 && st <= L) add(tr, bp::RK_ROUND, idx, st - 1, B * 4 * (n >> st), 64);
-                    if (sl.dev.defer && st >= defer_first && st <= msm_last(L)) {   // a chunk of the split stage 0
-                        unsigned long long lo, hi;
-                        msm_chunk(bp::stage0_lanes(B, n, L, range_mode, bp::S0_DEFER).total, L, st, lo, hi);
-                        add(tr, bp::RK_MSMT, idx, (int)lo, hi - lo, 64);
-                    }
-                    if (st == g.ft) add(tr, bp::RK_FINAL_TERMS, idx, 0, B * 2, 64);
-                    if (st == g.m3) add(tr, bp::RK_M3, idx, 0, B * 2, 64);
-                }
-            }
-        }
-        if (overflow) { g_err = "pipeline region list overflow (internal)"; return HIPBP_ERR_ARG; }
-        // Drain-tick form: a tick whose scalar multiplications cannot fill the SIMDs (the last
-        // fold rounds and final terms of the last batches, a one-proof verify) lasts one
-        // scalar-multiplication chain's latency; its items then take a lane quad each (k_terms<4>,
-        // 3 product latencies per point op instead of 9).  HIPBP_QUAD=0/1 forces it off/on;
-        // HIPBP_QUAD_MAX_ITEMS sets the tick's scalar-multiplication items up to which it is used.
-        unsigned long long sm_items = 0;
-        for (int k = 0; k < tr.count; k++)
-            if (bp::region_is_sm(tr.reg[k].kind)) sm_items += tr.reg[k].items;
-        // Between the two (up to PAIR_MAX_ITEMS), lane pairs (HIPBP_QUAD=2 forces them,
-        // HIPBP_PAIR_MAX_ITEMS sets the bound).
-        int ql = sm_items <= row_max ? 16 : sm_items <= quad_max ? 4 : sm_items <= pair_max ? 2 : 1;
-        if (!sm_items) {   // a tick of chains alone: the chains on quads, in the row-form kernel when the
-            // tick is small (a one-proof call's ticks then load one tick code object, not two)
-            unsigned long long chain_items = 0;
-            for (int k = 0; k < tr.count; k++) chain_items += tr.reg[k].items;
-            ql = chain_items <= row_max ? 16 : 4;
-        }
-        if (quad_force >= 0) ql = quad_force;
-        if (ql > 1) {   // re-lay the regions: scalar-multiplication items ql lanes each
-            unsigned long long tot = 0;
-            for (int k = 0; k < tr.count; k++) {
-                bp::Region& g = tr.reg[k];
-                g.items *= bp::region_lanes(g.kind, ql);
-                g.begin = tot;
-                const unsigned long long al = g.kind == bp::RK_TREE ? 256 : 64;
-                tot += (g.items + al - 1) & ~(al - 1);
-            }
-            tr.total = tot;
-        }
-        if (tr.total >= (1ull << 32)) { g_err = "pipeline tick exceeds 2^32 lanes (batch too large for n)"; return HIPBP_ERR_ARG; }
+        bp::TickPlan tick;
+        const bp::PlanError pe = bp::plan_tick(cfg, ring, D, head, tick);
+        if (pe == bp::PLAN_OVERFLOW) { g_err = "pipeline region list overflow (internal)"; return HIPBP_ERR_ARG; }
+        if (pe == bp::PLAN_TOO_LARGE) { g_err = "pipeline tick exceeds 2^32 lanes (batch too large for n)"; return HIPBP_ERR_ARG; }
         if (tm) tm->mark(bp::KT_TERMS, false, s);
-        bp::launch_terms(tr, slots_dev, G, H, g ? g : h, h, e->dtab, e->two_i, s, ql);
+        bp::launch_terms(tick.rl, slots_dev, G, H, g ? g : h, h, e->dtab, e->two_i, s, tick.ql);
         if (tm) tm->mark(bp::KT_TERMS, true, s);
         BP_RET_ON(hipGetLastError());
         if (has && plan.count) {   // the new batch's scalars exist now (its RK_PREP ran): order its lanes
-            if (sort_s) {   // tick -> sort (high priority) -> the pipeline's next tick
-                BP_RET_ON(hipEventRecord(ev_tick, s));
-                BP_RET_ON(hipStreamWaitEvent(sort_s, ev_tick, 0));
-                bp::launch_lane_sort(plan, sort_bins.as<unsigned>(), sort_offs.as<unsigned>(), sort_s);
-                BP_RET_ON(hipGetLastError());
-                BP_RET_ON(hipEventRecord(ev_sorted, sort_s));
-                BP_RET_ON(hipStreamWaitEvent(s, ev_sorted, 0));
-            } else {
-                bp::launch_lane_sort(plan, sort_bins.as<unsigned>(), sort_offs.as<unsigned>(), s);
-                BP_RET_ON(hipGetLastError());
-            }
+            bp::launch_lane_sort(plan, sort_bins.as<unsigned>(), sort_offs.as<unsigned>(), s);
+            BP_RET_ON(hipGetLastError());
         }
-        for (auto& sl : slots) {
-            if (!sl.active) continue;
-            if (sl.stage == stages(sl.dev.bv.L_len).fin) sl.active = false;
-            else sl.stage++;
-        }
-        head = (head + 1) % D;
+        bp::advance_ring(cfg, ring, D, head);
         return HIPBP_OK;
     }
     int flush() {
@@ -783,7 +578,7 @@ int pipeline_for(Engine& e, hipStream_t s, size_t max_batch, int n, int range_mo
         return HIPBP_OK;
     }
     Pipeline* pl = new Pipeline();
-    hipError_t ierr = pl->init(&e, s, max_batch, n, range_mode);
+    hipError_t ierr = pl->init(&e, s, n, range_mode);
     if (ierr != hipSuccess) {
         pl->release();
         delete pl;
@@ -945,7 +740,7 @@ void* hipbp_pipeline_create(size_t max_batch, size_t n, int range_mode, const ge
         }
     }
     Pipeline* pl = new Pipeline();
-    err = pl->init(e, pick(stream, *e), max_batch, (int)n, range_mode);
+    err = pl->init(e, pick(stream, *e), (int)n, range_mode);
     if (err != hipSuccess) {
         g_err = std::string("pipeline init: ") + hipGetErrorString(err);
         pl->release();
@@ -1500,7 +1295,7 @@ int hipbp_pipeline_use_gens(void* handle, void* gens) {
 int hipbp_pipeline_defer_msm(void* handle, int on) {
     Pipeline* pl = (Pipeline*)handle;
     if (!pl) { g_err = "null pipeline"; return HIPBP_ERR_ARG; }
-    if (on && !pl->defer_ok()) {
+    if (on && !bp::defer_ok(pl->cfg)) {
         g_err = "defer_msm: needs cuda_range_proof_verify / range_proof_verify semantics, 4 <= n <= the lane-tree limit "
                 "and n <= 512 (a split tick's region list)";
         return HIPBP_ERR_ARG;

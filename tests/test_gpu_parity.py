@@ -1482,7 +1482,7 @@ def test_pipeline_quad_ticks_same_bits(bp, oracle, monkeypatch, n, B, mode, K, p
 def test_pipeline_deferred_msm_same_bits(bp, oracle, monkeypatch, n, B, mode, K, pushes, q):
     """Split stage 0 (hipbp_pipeline_defer_msm: the MSM terms, t*h and c*Q as RK_MSMT chunks inside
     the batch's own fold-round ticks, stages 2 .. L, on the pipeline's stream; the lane trees at
-    msm_last(L) + 1, the final-terms tick) gives the unsplit pipeline's verdicts, P, check points,
+    stage L + 1, the final-terms tick) gives the unsplit pipeline's verdicts, P, check points,
     mode-2 flags and polynomial sides bit for bit: batches in flight together, with and without
     prefix tables, each tick form; a sample equals the oracle."""
     from cudabulletproof_amd import synth

@@ -11,7 +11,7 @@ process per run under its own time limit; the first failing run ends the A/B (no
 
   (replaces the round 1-4 scripts ab_env / ab_libs / ab_pipes / ab_prefix_bits / ab_prove_gate /
    ab_run / ab_shard_env / ab_prove / ab_streams: e.g. a library A/B is --cfg "base: lib:ab/lib_base.so"
-   --cfg "occ3: lib:ab/lib_occ3.so", an environment A/B --cfg "gate: env:HIPBP_PROVE_GATE=1")
+   --cfg "occ3: lib:ab/lib_occ3.so", an environment A/B --cfg "split: env:HIPBP_DEFER_MSM=1")
 
 Writes gpurun_out/ab/<tag>_<name>_r<rep>.json (the bench line) and gpurun_out/ab/<tag>.json
 (every run's picked fields + per-configuration medians) and prints one row per run.
