@@ -24,7 +24,7 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libcudabulletproof_hip.so")
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["bp_terms1.hip", "bp_terms2.hip", "bp_terms4.hip", "bp_terms16.hip", "bp_kernels.hip", "bp_prove.hip",
-           "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_capi.hip"]
+           "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_capi.hip"]
 
 _lib = None
 
@@ -126,6 +126,8 @@ EXPORTS = [
     "hipbp_pipeline_defer_msm",
     "hipbp_release_stream_workspaces",
     "hipbp_batch_inner_product_prove", "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host",
+    "hipbp_derive_prover_scalars", "hipbp_batch_generate_range_proof_seeded",
+    "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host",
 ]
 
 
@@ -153,7 +155,9 @@ def lib():
                   "hipbp_msm_pippenger_horner", "hipbp_msm_batch", "hipbp_msm_batch_gens", "hipbp_point_tree",
                   "hipbp_field_op", "hipbp_sha_probe", "hipbp_sync", "hipbp_device_count",
                   "hipbp_release_stream_workspaces", "hipbp_batch_inner_product_prove",
-                  "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host"):
+                  "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host",
+                  "hipbp_derive_prover_scalars", "hipbp_batch_generate_range_proof_seeded",
+                  "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host"):
             getattr(L, f).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -482,6 +486,115 @@ def batch_generate_range_proof(n, v, gamma, sL, sR, rnd, G, H, g, h, stream=None
                                                     _stream_ptr(stream)))
     out["_keep"] = ins
     return out
+
+
+# ---------------------------------------------------------------------- seeded prover
+_PROOF_KEYS = ("V", "A", "S", "T1", "T2", "taux", "mu", "t", "c", "x", "a", "b", "L", "R", "valid")
+
+
+def _seed_arg(seed):
+    """The 32 secret seed bytes as a ctypes buffer (the C ABI reads them during the call)."""
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError(f"seed must be 32 bytes, got {len(seed)}")
+    return (ctypes.c_uint8 * 32).from_buffer_copy(seed)
+
+
+def derive_prover_scalars(n, v, gamma, seed, index_base=0, stream=None):
+    """hipbp_derive_prover_scalars: the seeded prover's derivation alone, on the GPU.
+
+    v, gamma (B,4) int64 CUDA tensors of the u64 limbs; seed: 32 secret bytes; proof p of the call
+    has the global index index_base + p (mod 2^64).  Returns dict(sL (B,n,4), sR (B,n,4), rnd (B,4,4))
+    of int64 CUDA tensors: what batch_generate_range_proof takes and what
+    batch_generate_range_proof_seeded proves with."""
+    import contextlib
+
+    import torch
+    sd = _seed_arg(seed)
+    B, n = int(v.shape[0]), int(n)
+    ins = [v.contiguous(), gamma.contiguous()]
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=v.device)
+        out = dict(sL=z(B, n, 4), sR=z(B, n, 4), rnd=z(B, 4, 4))
+    _chk(lib().hipbp_derive_prover_scalars(sd, _c(ins[0].data_ptr()), _c(ins[1].data_ptr()),
+                                           ctypes.c_uint64(int(index_base) & (2**64 - 1)), _sz(B), _sz(n),
+                                           _c(out["sL"].data_ptr()), _c(out["sR"].data_ptr()),
+                                           _c(out["rnd"].data_ptr()), _stream_ptr(stream)))
+    out["_keep"] = ins
+    return out
+
+
+def batch_generate_range_proof_seeded(n, v, gamma, seed, G, H, g, h, index_base=0, stream=None, gens=None):
+    """batch_generate_range_proof with its random scalars derived on the GPU from a 32-byte secret
+    seed (hipbp_batch_generate_range_proof_seeded; derivation: DESIGN §13): the proofs of
+    batch_generate_range_proof(n, v, gamma, **derive_prover_scalars(n, v, gamma, seed, index_base)),
+    bit for bit, without the scalars ever being the caller's.  v, gamma (B,4) int64 CUDA tensors;
+    proof p has the global index index_base + p, so a batch cut into several calls gives the proofs
+    of the single call.  Returns batch_generate_range_proof's dict."""
+    import contextlib
+
+    import torch
+    sd = _seed_arg(seed)
+    B = int(v.shape[0])
+    Lr = max(int(n).bit_length() - 1, 0)
+    dev = v.device
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+        out = dict(V=z(B, 16), A=z(B, 16), S=z(B, 16), T1=z(B, 16), T2=z(B, 16), taux=z(B, 4), mu=z(B, 4),
+                   t=z(B, 4), c=z(B, 4), x=z(B, 4), a=z(B, 1, 4), b=z(B, 1, 4), L=z(B, Lr, 16), R=z(B, Lr, 16),
+                   valid=torch.empty(B, dtype=torch.uint8, device=dev))
+    ins = [v.contiguous(), gamma.contiguous()]
+    ic = ProveInputC(B, int(n), ins[0].data_ptr(), ins[1].data_ptr(), None, None, None)
+    oc = ProofOutC(*[out[k].data_ptr() if out[k].numel() else None for k in _PROOF_KEYS])
+    ib = ctypes.c_uint64(int(index_base) & (2**64 - 1))
+    if gens is not None:   # the set's generators and prefix tables (G, H, g, h are not read)
+        _chk(lib().hipbp_batch_generate_range_proof_seeded_gens(ctypes.byref(ic), sd, ib, _c(gens.h), ctypes.byref(oc),
+                                                                _stream_ptr(stream)))
+    else:
+        _chk(lib().hipbp_batch_generate_range_proof_seeded(ctypes.byref(ic), sd, ib, _c(G.data_ptr()), _c(H.data_ptr()),
+                                                           _c(g.data_ptr()), _c(h.data_ptr()), ctypes.byref(oc),
+                                                           _stream_ptr(stream)))
+    out["_keep"] = ins
+    return out
+
+
+def batch_generate_range_proof_host(v, gamma, n, G, H, g, h, seed, index_base=0):
+    """hipbp_batch_generate_range_proof_host: the seeded prover on host arrays, through the
+    reference's own RangeProof structs.  v, gamma (count,4), G, H (n,16), g, h (16,) uint64; seed 32
+    secret bytes.  Returns (proofs, valid): a list of the proof dicts cuda_range_proof_verify and
+    batch_range_proof_verify_host take (head (100,) = V,A,S,T1,T2 | taux,mu,t,c,x; a, b (1,4); L, R
+    (log2 n,16)) and a (count,) bool array.  A refused value (valid False) has the zeroed proof:
+    empty a, b, L, R.  Synchronous, on the current device."""
+    require_gpu()
+    sd = _seed_arg(seed)
+    v, gamma = _u64(v, 4).reshape(-1, 4), _u64(gamma, 4).reshape(-1, 4)
+    if len(v) != len(gamma):
+        raise ValueError("v and gamma must have the same length")
+    G, H, g, h = _u64(G, 16), _u64(H, 16), _u64(g, 16), _u64(h, 16)
+    count = len(v)
+    arr = (RangeProofC * max(count, 1))()
+    valid = np.zeros(max(count, 1), np.uint8)
+    gv, hv = PointVector(_p(G).value, len(G)), PointVector(_p(H).value, len(H))
+    _chk(lib().hipbp_batch_generate_range_proof_host(arr, _p(valid), _p(v), _p(gamma), _sz(count), _sz(int(n)),
+                                                     ctypes.byref(gv), ctypes.byref(hv), _p(g), _p(h), sd,
+                                                     ctypes.c_uint64(int(index_base) & (2**64 - 1))))
+    libc = ctypes.CDLL(None)
+    libc.free.argtypes = [ctypes.c_void_p]
+
+    def take(vec, words):
+        out = np.ctypeslib.as_array(ctypes.cast(vec.elements, ctypes.POINTER(ctypes.c_uint64)),
+                                    shape=(vec.length, words)).copy() if vec.length else np.zeros((0, words), np.uint64)
+        libc.free(vec.elements)
+        return out
+    proofs = []
+    for i in range(count):
+        rp = arr[i]
+        ip = rp.ip_proof
+        head = np.concatenate([np.array(getattr(rp, k), np.uint64) for k in ("V", "A", "S", "T1", "T2", "taux", "mu", "t")] +
+                              [np.array(ip.c, np.uint64), np.array(ip.x, np.uint64)])
+        proofs.append(dict(head=head, a=take(ip.a, 4), b=take(ip.b, 4), L=take(ip.L, 16), R=take(ip.R, 16),
+                           n=int(ip.n), L_len=int(ip.L_len)))
+    return proofs, valid[:count].astype(bool)
 
 
 def batch_inner_product_prove(n, a, b, c, G, H, Q, transcript=None, stream=None, gens=None):

@@ -21,6 +21,7 @@
 #include "../../include/cudabulletproof_hip.h"
 #include "bp_tick_plan.h"
 #include "ge25519_dev.h"
+#include "bp_prove_seed.h"
 
 static_assert(sizeof(fe25519) == 32, "fe25519 layout");
 static_assert(sizeof(ge25519) == 128, "ge25519 layout");
@@ -161,6 +162,21 @@ struct Engine {
         Buf b[19];
     };
     std::map<hipStream_t, ProverBufs*> provers;
+    // seeded prover (hipbp_batch_generate_range_proof_seeded): the derived scalars of a batch, rnd | sL |
+    // sR, and the per-proof keys, one set per stream like the prover's own buffers.  seed_mu is held
+    // from the derive launches to the end of the prover's enqueue (taken before `mu`), so two host
+    // threads on one stream cannot interleave a derivation between another's derivation and its prover.
+    struct SeedBufs {
+        Buf keys, scal;
+    };
+    std::map<hipStream_t, SeedBufs*> seed_ws;
+    std::mutex seed_mu;
+    // hipbp_batch_generate_range_proof_host: its own staging (pinned host + device, two chunk slots and
+    // the generators), grow-only, guarded by prove_host_mu (taken before seed_mu and mu)
+    Buf prove_host_dev;
+    uint8_t* prove_host_pinned = nullptr;
+    size_t prove_host_pinned_cap = 0;
+    std::mutex prove_host_mu;
     // stand-alone IPA prover workspaces (hipbp_batch_inner_product_prove), per caller stream: two
     // chunk workspaces, the second run on an internal side stream so one chunk's latency-bound
     // chains run under the other's scalar multiplications (the Pippenger path's scheme)
@@ -923,6 +939,13 @@ int hipbp_release_stream_workspaces(void* stream) {
         delete pi->second;
         e->provers.erase(pi);
     }
+    auto si = e->seed_ws.find(s);
+    if (si != e->seed_ws.end()) {
+        free_all(&si->second->keys, 1);
+        free_all(&si->second->scal, 1);
+        delete si->second;
+        e->seed_ws.erase(si);
+    }
     auto ii = e->ipa_ws.find(s);
     if (ii != e->ipa_ws.end()) {
         Engine::IpaBufs* ib = ii->second;
@@ -1092,6 +1115,267 @@ int hipbp_batch_generate_range_proof_gens(const hipbp_prove_input* in, void* gen
     if (dev != gs->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
     return prove_run(in, (const ge25519*)gs->G(), (const ge25519*)gs->H(), (const ge25519*)gs->g(),
                      (const ge25519*)gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits, out, stream);
+}
+
+// ---- seeded prover (bp_prove_seed.h / .hip): the prover's random scalars derived on the device
+// from a 32-byte seed.  seed_check: the shape limits of prove_run, checked before anything is
+// enqueued (the derive kernels index with them).
+static int seed_check(const uint8_t* seed32, const fe25519* v, const fe25519* gamma, size_t count, size_t n) {
+    if (!seed32) { g_err = "seeded prover: null seed"; return HIPBP_ERR_ARG; }
+    if (!is_pow2(n) || n > 128) { g_err = "prover: n must be a power of two <= 128"; return HIPBP_ERR_ARG; }
+    if (count > ((size_t)1 << 22)) { g_err = "prover: batch too large"; return HIPBP_ERR_ARG; }
+    if (!v || !gamma) { g_err = "prover: null input"; return HIPBP_ERR_ARG; }
+    return HIPBP_OK;
+}
+
+// the key workspace of stream s (e.mu held by the caller), grown to B keys
+static int seed_keys(Engine& e, hipStream_t s, size_t B, Engine::SeedBufs** out) {
+    Engine::SeedBufs*& sb = e.seed_ws[s];
+    if (!sb) sb = new Engine::SeedBufs();
+    BP_RET_ON(sb->keys.need(B * sizeof(bp::fe)));
+    *out = sb;
+    return HIPBP_OK;
+}
+
+int hipbp_derive_prover_scalars(const uint8_t* seed32, const fe25519* v, const fe25519* gamma, uint64_t index_base,
+                                size_t count, size_t n, fe25519* sL, fe25519* sR, fe25519* rnd, void* stream) {
+    hipError_t err;
+    Engine* e = engine_or_null(&err);
+    BP_RET_ON(err);
+    int rc = seed_check(seed32, v, gamma, count, n);
+    if (rc != HIPBP_OK) return rc;
+    if (!sL || !sR || !rnd) { g_err = "derive: null output"; return HIPBP_ERR_ARG; }
+    if (count == 0) return HIPBP_OK;
+    hipStream_t s = pick(stream, *e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    Engine::SeedBufs* sb = nullptr;
+    if ((rc = seed_keys(*e, s, count, &sb)) != HIPBP_OK) return rc;
+    bp::launch_seed_derive(bp::seed_words(seed32), (const bp::fe*)v, (const bp::fe*)gamma, index_base, (uint32_t)count,
+                           (uint32_t)n, sb->keys.as<bp::fe>(), (bp::fe*)sL, (bp::fe*)sR, (bp::fe*)rnd, s);
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+static int prove_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base, const ge25519* G,
+                        const ge25519* H, const ge25519* g, const ge25519* h, const bp::ge* ptab, int pbits,
+                        hipbp_proof_out* out, void* stream) {
+    hipError_t err;
+    Engine* e = engine_or_null(&err);
+    BP_RET_ON(err);
+    if (!in || !out || !G || !H || !g || !h) { g_err = "null argument"; return HIPBP_ERR_ARG; }
+    if (in->sL || in->sR || in->rnd) {
+        g_err = "seeded prover: sL, sR and rnd must be NULL (the scalars are derived from the seed)";
+        return HIPBP_ERR_ARG;
+    }
+    int rc = seed_check(seed32, in->v, in->gamma, in->count, in->n);
+    if (rc != HIPBP_OK) return rc;
+    if (in->count == 0) return HIPBP_OK;
+    const size_t B = in->count, n = in->n;
+    hipStream_t s = pick(stream, *e);
+    std::lock_guard<std::mutex> slk(e->seed_mu);
+    bp::fe* scal = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        Engine::SeedBufs* sb = nullptr;
+        if ((rc = seed_keys(*e, s, B, &sb)) != HIPBP_OK) return rc;
+        BP_RET_ON(sb->scal.need(B * (2 * n + 4) * sizeof(bp::fe)));   // rnd [B*4] | sL [B*n] | sR [B*n]
+        scal = sb->scal.as<bp::fe>();
+        bp::launch_seed_derive(bp::seed_words(seed32), (const bp::fe*)in->v, (const bp::fe*)in->gamma, index_base,
+                               (uint32_t)B, (uint32_t)n, sb->keys.as<bp::fe>(), scal + 4 * B, scal + (4 + n) * B, scal,
+                               s);
+        BP_RET_ON(hipGetLastError());
+    }
+    hipbp_prove_input full = *in;
+    full.rnd = (const fe25519*)scal;
+    full.sL = (const fe25519*)(scal + 4 * B);
+    full.sR = (const fe25519*)(scal + (4 + n) * B);
+    return prove_run(&full, G, H, g, h, ptab, pbits, out, stream);
+}
+
+int hipbp_batch_generate_range_proof_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base,
+                                            const ge25519* G, const ge25519* H, const ge25519* g, const ge25519* h,
+                                            hipbp_proof_out* out, void* stream) {
+    return prove_seeded(in, seed32, index_base, G, H, g, h, nullptr, 0, out, stream);
+}
+
+int hipbp_batch_generate_range_proof_seeded_gens(const hipbp_prove_input* in, const uint8_t* seed32,
+                                                 uint64_t index_base, void* gens, hipbp_proof_out* out, void* stream) {
+    Gens* gs = (Gens*)gens;
+    if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
+    if (!in || in->n != gs->n) { g_err = "prover: input n differs from the generator set's"; return HIPBP_ERR_ARG; }
+    int dev = -1;
+    BP_RET_ON(hipGetDevice(&dev));
+    if (dev != gs->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    return prove_seeded(in, seed32, index_base, (const ge25519*)gs->G(), (const ge25519*)gs->H(),
+                        (const ge25519*)gs->g(), (const ge25519*)gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr,
+                        gs->bits, out, stream);
+}
+
+// The seeded prover on host data.  The batch goes through in chunks that alternate over the
+// engine's two streams and two staging slots: a slot's previous chunk is unpacked into the caller's
+// structs (after its stream is drained) before the slot's next chunk is staged, so one chunk's
+// copies and unpacking run under the other's kernels.  Slot layout (pinned host and device alike):
+// v | gamma [c] | V A S T1 T2 [c] | taux mu t c x a b [c] | L R [c Lr] | valid [c].
+int hipbp_batch_generate_range_proof_host(RangeProof* proofs, uint8_t* valid, const fe25519* v, const fe25519* gamma,
+                                          size_t count, size_t n, const PointVector* G, const PointVector* H,
+                                          const ge25519* g, const ge25519* h, const uint8_t seed32[32],
+                                          uint64_t index_base) {
+    if (count == 0) return HIPBP_OK;
+    if (!proofs || !valid || !G || !H || !g || !h || !G->elements || !H->elements) {
+        g_err = "null argument";
+        return HIPBP_ERR_ARG;
+    }
+    int rc = seed_check(seed32, v, gamma, 0, n);
+    if (rc != HIPBP_OK) return rc;
+    if (G->length != n || H->length != n) { g_err = "prover: G and H must hold n generators"; return HIPBP_ERR_ARG; }
+    hipError_t err;
+    Engine* e = engine_or_null(&err);
+    BP_RET_ON(err);
+    size_t CH = 16384;
+    if (const char* ce = getenv("HIPBP_PROVE_HOST_CHUNK"))
+        if (atol(ce) > 0) CH = std::min<size_t>((size_t)atol(ce), (size_t)1 << 22);
+    CH = std::min(CH, count);
+    const size_t GE = sizeof(ge25519), FE = sizeof(fe25519), Lr = (size_t)log2i(n);
+    const size_t o_pts = 2 * CH * FE, o_fe = o_pts + 5 * CH * GE, o_lr = o_fe + 7 * CH * FE;
+    const size_t o_valid = o_lr + 2 * CH * Lr * GE, slot_bytes = (o_valid + CH + 127) & ~(size_t)127;
+    const size_t gen_off = 2 * slot_bytes, bytes = gen_off + (2 * n + 2) * GE;
+    memset(proofs, 0, count * sizeof(RangeProof));
+    memset(valid, 0, count);
+    std::lock_guard<std::mutex> hlk(e->prove_host_mu);
+    hipStream_t st[2];
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (!e->stream2) BP_RET_ON(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
+        st[0] = e->stream;
+        st[1] = e->stream2;
+    }
+    // (calls of this function serialise on prove_host_mu and each ends with both streams drained
+    // of its work, so nothing still reads the staging when it grows)
+    if (bytes > e->prove_host_pinned_cap) {
+        if (e->prove_host_pinned) {
+            BP_RET_ON(hipHostFree(e->prove_host_pinned));
+            e->prove_host_pinned = nullptr;
+            e->prove_host_pinned_cap = 0;
+        }
+        BP_RET_ON(hipHostMalloc((void**)&e->prove_host_pinned, bytes));
+        e->prove_host_pinned_cap = bytes;
+    }
+    BP_RET_ON(e->prove_host_dev.need(bytes));
+    uint8_t* host = e->prove_host_pinned;
+    uint8_t* dbuf = e->prove_host_dev.as<uint8_t>();
+    memcpy(host + gen_off, G->elements, n * GE);
+    memcpy(host + gen_off + n * GE, H->elements, n * GE);
+    memcpy(host + gen_off + 2 * n * GE, g, GE);
+    memcpy(host + gen_off + (2 * n + 1) * GE, h, GE);
+    const ge25519* dG = (const ge25519*)(dbuf + gen_off);
+
+    size_t filled = 0;   // proofs[0 .. filled) may own malloc'ed vectors
+    auto fail = [&](int code, const std::string& what) {
+        g_err = what;
+        (void)hipStreamSynchronize(st[0]);   // nothing in flight reads the staging any more
+        (void)hipStreamSynchronize(st[1]);
+        for (size_t i = 0; i < filled; i++) {
+            InnerProductProof& ip = proofs[i].ip_proof;
+            free(ip.a.elements); free(ip.b.elements); free(ip.L.elements); free(ip.R.elements);
+        }
+        memset(proofs, 0, count * sizeof(RangeProof));
+        memset(valid, 0, count);
+        return code;
+    };
+    auto dev_fail = [&](hipError_t er, const char* what) {
+        return fail(HIPBP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(er));
+    };
+    // chunk [c0, c0 + c) out of its slot's pinned staging into the caller's structs
+    auto unpack = [&](size_t c0, size_t c, const uint8_t* hs) -> bool {
+        const ge25519* pts = (const ge25519*)(hs + o_pts);
+        const fe25519* f = (const fe25519*)(hs + o_fe);
+        const ge25519* lr = (const ge25519*)(hs + o_lr);
+        const uint8_t* vd = hs + o_valid;
+        for (size_t k = 0; k < c; k++) {
+            RangeProof& p = proofs[c0 + k];
+            p.V = pts[k]; p.A = pts[c + k]; p.S = pts[2 * c + k]; p.T1 = pts[3 * c + k]; p.T2 = pts[4 * c + k];
+            p.taux = f[k]; p.mu = f[c + k]; p.t = f[2 * c + k];
+            filled = c0 + k + 1;
+            valid[c0 + k] = vd[k] ? 1 : 0;
+            if (!vd[k]) continue;   // the zeroed proof: ip_proof stays all zero
+            InnerProductProof& ip = p.ip_proof;
+            ip.a.elements = (fe25519*)malloc(FE);
+            ip.b.elements = (fe25519*)malloc(FE);
+            ip.L.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
+            ip.R.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
+            if (!ip.a.elements || !ip.b.elements || !ip.L.elements || !ip.R.elements) return false;
+            ip.n = n;
+            ip.c = f[3 * c + k];
+            ip.x = f[4 * c + k];
+            *ip.a.elements = f[5 * c + k];
+            *ip.b.elements = f[6 * c + k];
+            ip.a.length = ip.b.length = 1;
+            if (Lr) {
+                memcpy(ip.L.elements, lr + k * Lr, Lr * GE);
+                memcpy(ip.R.elements, lr + (c + k) * Lr, Lr * GE);
+            }
+            ip.L.length = ip.R.length = ip.L_len = Lr;
+        }
+        return true;
+    };
+
+    if ((err = hipMemcpyAsync(dbuf + gen_off, host + gen_off, (2 * n + 2) * GE, hipMemcpyHostToDevice, st[0])) != hipSuccess)
+        return dev_fail(err, "generators H2D");
+    hipEvent_t gens_ready = nullptr;
+    if ((err = hipEventCreateWithFlags(&gens_ready, hipEventDisableTiming)) != hipSuccess) return dev_fail(err, "event");
+    if ((err = hipEventRecord(gens_ready, st[0])) == hipSuccess) err = hipStreamWaitEvent(st[1], gens_ready, 0);
+    if (err != hipSuccess) {
+        (void)hipEventDestroy(gens_ready);
+        return dev_fail(err, "generators event");
+    }
+    const size_t nch = (count + CH - 1) / CH;
+    rc = HIPBP_OK;
+    std::string what;
+    for (size_t ch = 0; ch < nch + 2 && rc == HIPBP_OK; ch++) {
+        const int k = (int)(ch & 1);
+        uint8_t* hs = host + k * slot_bytes;
+        uint8_t* ds = dbuf + k * slot_bytes;
+        if (ch >= 2) {   // the slot's previous chunk: wait for its D2H, hand it to the caller
+            const size_t p0 = (ch - 2) * CH, pc = std::min(CH, count - p0);
+            if ((err = hipStreamSynchronize(st[k])) != hipSuccess) {
+                rc = HIPBP_ERR_DEVICE;
+                what = std::string("chunk sync: ") + hipGetErrorString(err);
+                break;
+            }
+            if (!unpack(p0, pc, hs)) {
+                rc = HIPBP_ERR_DEVICE;
+                what = "Failed to allocate memory for a proof's vectors";
+                break;
+            }
+        }
+        if (ch >= nch) continue;
+        const size_t c0 = ch * CH, c = std::min(CH, count - c0);
+        memcpy(hs, v + c0, c * FE);
+        memcpy(hs + c * FE, gamma + c0, c * FE);
+        if ((err = hipMemcpyAsync(ds, hs, 2 * c * FE, hipMemcpyHostToDevice, st[k])) != hipSuccess) {
+            rc = HIPBP_ERR_DEVICE;
+            what = std::string("chunk H2D: ") + hipGetErrorString(err);
+            break;
+        }
+        ge25519* dp = (ge25519*)(ds + o_pts);
+        fe25519* df = (fe25519*)(ds + o_fe);
+        ge25519* dl = (ge25519*)(ds + o_lr);
+        hipbp_prove_input in{c, n, (const fe25519*)ds, (const fe25519*)ds + c, nullptr, nullptr, nullptr};
+        hipbp_proof_out out{dp, dp + c, dp + 2 * c, dp + 3 * c, dp + 4 * c,
+                            df, df + c, df + 2 * c, df + 3 * c, df + 4 * c, df + 5 * c, df + 6 * c,
+                            Lr ? dl : nullptr, Lr ? dl + c * Lr : nullptr, ds + o_valid};
+        rc = prove_seeded(&in, seed32, index_base + c0, dG, dG + n, dG + 2 * n, dG + 2 * n + 1, nullptr, 0, &out, st[k]);
+        if (rc != HIPBP_OK) { what = g_err; break; }
+        // one D2H of the slot's output regions, points .. valid[c) (the regions are sized for a full
+        // chunk; a short last chunk's arrays sit packed at the front of each)
+        if ((err = hipMemcpyAsync(hs + o_pts, ds + o_pts, o_valid + c - o_pts, hipMemcpyDeviceToHost, st[k])) != hipSuccess) {
+            rc = HIPBP_ERR_DEVICE;
+            what = std::string("chunk D2H: ") + hipGetErrorString(err);
+        }
+    }
+    (void)hipEventDestroy(gens_ready);
+    if (rc != HIPBP_OK) return fail(rc, what);
+    return HIPBP_OK;
 }
 
 // ---- stand-alone IPA prover (bp_ipa_prove.hip).  The engine's lock is held by the caller.

@@ -249,6 +249,52 @@ int hipbp_batch_generate_range_proof(const hipbp_prove_input* in, const ge25519*
 int hipbp_batch_generate_range_proof_gens(const hipbp_prove_input* in, void* gens, hipbp_proof_out* out,
                                           void* stream);
 
+/* ---- seeded prover (no reference counterpart): the 2n + 4 random scalars of every proof derived
+ * on the GPU from one 32-byte SECRET seed, so a caller supplies values, blindings and the seed
+ * instead of 2n + 4 scalars of 32 bytes per proof.  Byte-exact derivation, all integers little-endian:
+ *   key_p  = SHA-256("hipbpProverKeyV1" || seed[32] || v_p || gamma_p || LE64(index_base + p) || LE32(n))
+ *   d      = SHA-256("hipbpProverRndV1" || key_p || LE32(slot))
+ *   d[0] &= 0xF8; d[31] &= 0x7F; d[31] |= 0x40      (generate_random_scalar's masks, rp.cu:153-159)
+ *   scalar = d as 4 LE u64 limbs
+ * v_p, gamma_p: the 32 bytes of the four limbs as stored (not canonicalised); index_base + p wraps
+ * mod 2^64.  slot 0..3 = alpha, rho, tau1, tau2 (rnd's order), 4 + i = sL[i], 4 + n + i = sR[i].
+ * The key binds v, gamma and the proof's global index, so a seed reused with other values never
+ * reuses a nonce, and a batch cut into several calls (each with its own index_base) yields the
+ * proofs of the single call.  seed32 is a HOST pointer, read during the call (it travels in the
+ * kernel arguments); every other pointer is DEVICE memory.
+ *
+ * hipbp_derive_prover_scalars: the derivation alone, into sL[count*n], sR[count*n], rnd[count*4]
+ * (hipbp_prove_input's layout); asynchronous on `stream`.  n: power of two, 1..128; count <= 2^22;
+ * a bad n, count or a null pointer gives HIPBP_ERR_ARG and writes nothing. */
+int hipbp_derive_prover_scalars(const uint8_t* seed32, const fe25519* v, const fe25519* gamma, uint64_t index_base,
+                                size_t count, size_t n, fe25519* sL, fe25519* sR, fe25519* rnd, void* stream);
+/* hipbp_batch_generate_range_proof / _gens with derived scalars: in->sL, in->sR, in->rnd must be
+ * NULL (anything else: HIPBP_ERR_ARG, nothing written).  The scalars are derived into a workspace
+ * kept per (device, stream) (count (2n + 5) * 32 bytes: the scalars and the per-proof keys;
+ * hipbp_release_stream_workspaces frees it), then the explicit prover runs on them unchanged: the
+ * same bits as hipbp_derive_prover_scalars followed by the explicit call, the same argument
+ * checks, limits and valid = 0 zeroed proof.  Asynchronous on `stream`. */
+int hipbp_batch_generate_range_proof_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base,
+                                            const ge25519* G, const ge25519* H, const ge25519* g, const ge25519* h,
+                                            hipbp_proof_out* out, void* stream);
+int hipbp_batch_generate_range_proof_seeded_gens(const hipbp_prove_input* in, const uint8_t* seed32,
+                                                 uint64_t index_base, void* gens, hipbp_proof_out* out, void* stream);
+/* The seeded prover on host data: proofs[i] = the proof of (v[i], gamma[i]) under seed32 at index
+ * index_base + i, for i < count, with the bytes the device call gives.  Host pointers, synchronous,
+ * on the calling thread's current device.  n: power of two, 1..128, G->length = H->length = n.
+ * valid[i] = 1: proofs[i] is filled as hipbp_inner_product_prove_host fills its proof (ip_proof.n = n,
+ * a and b of length 1, L and R of L_len = log2 n, all malloc'ed, so the reference's range_proof_free
+ * frees them).  valid[i] = 0 (validate_range_input refused the value): the reference's zeroed proof
+ * (V, A, S, T1, T2 identity; taux, mu, t 0) with ip_proof all zero (NULL vectors: freeing is safe).
+ * Large counts go through in chunks (HIPBP_PROVE_HOST_CHUNK proofs, default 16384) that alternate
+ * over the engine's two streams, each chunk with its own index_base.  On an error nothing stays
+ * allocated and every proofs[i] is zero.  One device: a split over several devices would give
+ * the same bits by the index design and is left for later. */
+int hipbp_batch_generate_range_proof_host(RangeProof* proofs, uint8_t* valid, const fe25519* v, const fe25519* gamma,
+                                          size_t count, size_t n, const PointVector* G, const PointVector* H,
+                                          const ge25519* g, const ge25519* h, const uint8_t seed32[32],
+                                          uint64_t index_base);
+
 /* ---- prover: the stand-alone inner_product_prove (bulletproof_vectors.h:94,
  * bulletproof_vectors.cu:277-523) for any power-of-two length, batched, bit-exact: the reference's
  * sequential MSM chains and inner products in its order, the ORIGINAL G, H in every round, Q any
@@ -362,7 +408,7 @@ int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_
  * in0..in3 in raw limb order.  For checking against FIPS 180-4 (bulletproof_challenge.cu:6-77). */
 int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
- * point-tree, prover, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
+ * point-tree, prover, the seeded prover's scalars and keys, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
  * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
  * a caller that makes short-lived streams calls this before destroying one.  No reference
  * counterpart. */
