@@ -453,6 +453,25 @@ class Generators:
             pass
 
 
+_PROOF_KEYS = ("V", "A", "S", "T1", "T2", "taux", "mu", "t", "c", "x", "a", "b", "L", "R", "valid")
+
+
+def _proof_out(B, n, dev, stream):
+    """The prover's fifteen output tensors (_PROOF_KEYS) and the hipbp_proof_out over them.  Every
+    output element is written by the prover (refused proofs get the reference's zeroed proof), so the
+    buffers are allocated uninitialised on the stream the prover runs on."""
+    import contextlib
+
+    import torch
+    Lr = max(int(n).bit_length() - 1, 0)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+        out = dict(V=z(B, 16), A=z(B, 16), S=z(B, 16), T1=z(B, 16), T2=z(B, 16), taux=z(B, 4), mu=z(B, 4),
+                   t=z(B, 4), c=z(B, 4), x=z(B, 4), a=z(B, 1, 4), b=z(B, 1, 4), L=z(B, Lr, 16), R=z(B, Lr, 16),
+                   valid=torch.empty(B, dtype=torch.uint8, device=dev))
+    return out, ProofOutC(*[out[k].data_ptr() if out[k].numel() else None for k in _PROOF_KEYS])
+
+
 def batch_generate_range_proof(n, v, gamma, sL, sR, rnd, G, H, g, h, stream=None, gens=None):
     """generate_range_proof (bulletproof_range_proof.cu:1159) over a batch, on the GPU.
 
@@ -460,23 +479,10 @@ def batch_generate_range_proof(n, v, gamma, sL, sR, rnd, G, H, g, h, stream=None
     u64 limbs (the random scalars exactly as generate_random_scalar produced them).  Returns a dict
     of CUDA tensors in RangeProofBatch layout (V, A, S, T1, T2, t, a, b, c, x, L, R, taux, mu) plus
     "valid" (B,) uint8; RangeProofBatch(n, **out) verifies it directly."""
-    import contextlib
-
-    import torch
     B = int(v.shape[0])
-    Lr = int(n).bit_length() - 1
-    dev = v.device
-    # every output element is written by the prover (refused proofs get the reference's zeroed
-    # proof), so the buffers are allocated uninitialised on the stream the prover runs on
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
-        out = dict(V=z(B, 16), A=z(B, 16), S=z(B, 16), T1=z(B, 16), T2=z(B, 16), taux=z(B, 4), mu=z(B, 4),
-                   t=z(B, 4), c=z(B, 4), x=z(B, 4), a=z(B, 1, 4), b=z(B, 1, 4), L=z(B, max(Lr, 0), 16),
-                   R=z(B, max(Lr, 0), 16), valid=torch.empty(B, dtype=torch.uint8, device=dev))
+    out, oc = _proof_out(B, n, v.device, stream)
     ins = [t.contiguous() for t in (v, gamma, sL, sR, rnd)]
     ic = ProveInputC(B, int(n), *[t.data_ptr() for t in ins])
-    oc = ProofOutC(*[out[k].data_ptr() if out[k].numel() else None for k in
-                     ("V", "A", "S", "T1", "T2", "taux", "mu", "t", "c", "x", "a", "b", "L", "R", "valid")])
     if gens is not None:   # the set's generators and prefix tables (G, H, g, h are not read)
         _chk(lib().hipbp_batch_generate_range_proof_gens(ctypes.byref(ic), _c(gens.h), ctypes.byref(oc),
                                                          _stream_ptr(stream)))
@@ -489,9 +495,6 @@ def batch_generate_range_proof(n, v, gamma, sL, sR, rnd, G, H, g, h, stream=None
 
 
 # ---------------------------------------------------------------------- seeded prover
-_PROOF_KEYS = ("V", "A", "S", "T1", "T2", "taux", "mu", "t", "c", "x", "a", "b", "L", "R", "valid")
-
-
 def _seed_arg(seed):
     """The 32 secret seed bytes as a ctypes buffer (the C ABI reads them during the call)."""
     seed = bytes(seed)
@@ -531,21 +534,11 @@ def batch_generate_range_proof_seeded(n, v, gamma, seed, G, H, g, h, index_base=
     bit for bit, without the scalars ever being the caller's.  v, gamma (B,4) int64 CUDA tensors;
     proof p has the global index index_base + p, so a batch cut into several calls gives the proofs
     of the single call.  Returns batch_generate_range_proof's dict."""
-    import contextlib
-
-    import torch
     sd = _seed_arg(seed)
     B = int(v.shape[0])
-    Lr = max(int(n).bit_length() - 1, 0)
-    dev = v.device
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
-        out = dict(V=z(B, 16), A=z(B, 16), S=z(B, 16), T1=z(B, 16), T2=z(B, 16), taux=z(B, 4), mu=z(B, 4),
-                   t=z(B, 4), c=z(B, 4), x=z(B, 4), a=z(B, 1, 4), b=z(B, 1, 4), L=z(B, Lr, 16), R=z(B, Lr, 16),
-                   valid=torch.empty(B, dtype=torch.uint8, device=dev))
+    out, oc = _proof_out(B, n, v.device, stream)
     ins = [v.contiguous(), gamma.contiguous()]
     ic = ProveInputC(B, int(n), ins[0].data_ptr(), ins[1].data_ptr(), None, None, None)
-    oc = ProofOutC(*[out[k].data_ptr() if out[k].numel() else None for k in _PROOF_KEYS])
     ib = ctypes.c_uint64(int(index_base) & (2**64 - 1))
     if gens is not None:   # the set's generators and prefix tables (G, H, g, h are not read)
         _chk(lib().hipbp_batch_generate_range_proof_seeded_gens(ctypes.byref(ic), sd, ib, _c(gens.h), ctypes.byref(oc),
@@ -556,6 +549,21 @@ def batch_generate_range_proof_seeded(n, v, gamma, seed, G, H, g, h, index_base=
                                                            _stream_ptr(stream)))
     out["_keep"] = ins
     return out
+
+
+def _take(vec, words):
+    """A malloc'ed FieldVector / PointVector the library handed out, as a (length, words) uint64
+    array; the C vector is freed."""
+    if _take.free is None:
+        _take.free = ctypes.CDLL(None).free
+        _take.free.argtypes = [ctypes.c_void_p]
+    out = np.ctypeslib.as_array(ctypes.cast(vec.elements, ctypes.POINTER(ctypes.c_uint64)),
+                                shape=(vec.length, words)).copy() if vec.length else np.zeros((0, words), np.uint64)
+    _take.free(vec.elements)
+    return out
+
+
+_take.free = None   # libc's free, looked up on first use
 
 
 def batch_generate_range_proof_host(v, gamma, n, G, H, g, h, seed, index_base=0):
@@ -578,21 +586,13 @@ def batch_generate_range_proof_host(v, gamma, n, G, H, g, h, seed, index_base=0)
     _chk(lib().hipbp_batch_generate_range_proof_host(arr, _p(valid), _p(v), _p(gamma), _sz(count), _sz(int(n)),
                                                      ctypes.byref(gv), ctypes.byref(hv), _p(g), _p(h), sd,
                                                      ctypes.c_uint64(int(index_base) & (2**64 - 1))))
-    libc = ctypes.CDLL(None)
-    libc.free.argtypes = [ctypes.c_void_p]
-
-    def take(vec, words):
-        out = np.ctypeslib.as_array(ctypes.cast(vec.elements, ctypes.POINTER(ctypes.c_uint64)),
-                                    shape=(vec.length, words)).copy() if vec.length else np.zeros((0, words), np.uint64)
-        libc.free(vec.elements)
-        return out
     proofs = []
     for i in range(count):
         rp = arr[i]
         ip = rp.ip_proof
         head = np.concatenate([np.array(getattr(rp, k), np.uint64) for k in ("V", "A", "S", "T1", "T2", "taux", "mu", "t")] +
                               [np.array(ip.c, np.uint64), np.array(ip.x, np.uint64)])
-        proofs.append(dict(head=head, a=take(ip.a, 4), b=take(ip.b, 4), L=take(ip.L, 16), R=take(ip.R, 16),
+        proofs.append(dict(head=head, a=_take(ip.a, 4), b=_take(ip.b, 4), L=_take(ip.L, 16), R=_take(ip.R, 16),
                            n=int(ip.n), L_len=int(ip.L_len)))
     return proofs, valid[:count].astype(bool)
 
@@ -663,16 +663,8 @@ def inner_product_prove(a, b, G, H, Q, c, transcript=None):
         if not pr.a.elements and rc == 1:
             return None
         _chk(rc)
-    libc = ctypes.CDLL(None)
-    libc.free.argtypes = [ctypes.c_void_p]
-
-    def take(vec, words):
-        out = np.ctypeslib.as_array(ctypes.cast(vec.elements, ctypes.POINTER(ctypes.c_uint64)),
-                                    shape=(vec.length, words)).copy() if vec.length else np.zeros((0, words), np.uint64)
-        libc.free(vec.elements)
-        return out
-    return dict(a=take(pr.a, 4), b=take(pr.b, 4), c=np.array(pr.c, np.uint64), x=np.array(pr.x, np.uint64),
-                L=take(pr.L, 16), R=take(pr.R, 16), L_len=int(pr.L_len), n=int(pr.n))
+    return dict(a=_take(pr.a, 4), b=_take(pr.b, 4), c=np.array(pr.c, np.uint64), x=np.array(pr.x, np.uint64),
+                L=_take(pr.L, 16), R=_take(pr.R, 16), L_len=int(pr.L_len), n=int(pr.n))
 
 
 def msm(result, scalars, points, stream=None):

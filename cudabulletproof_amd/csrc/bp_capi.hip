@@ -7,7 +7,6 @@
 // keeps grow-only device buffers, the identity-doubling and 2^i tables, and one stream.
 #include <hip/hip_runtime.h>
 #include <map>
-#include <tuple>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -20,6 +19,7 @@
 
 #include "../../include/cudabulletproof_hip.h"
 #include "bp_tick_plan.h"
+#include "bp_layout.h"
 #include "ge25519_dev.h"
 #include "bp_prove_seed.h"
 
@@ -51,24 +51,45 @@ thread_local std::string g_err;
         }                                                                                     \
     } while (0)
 
-struct Buf {
+// A grow-only device buffer (Buf) or pinned host staging buffer (PinnedBuf).  need() frees the old
+// allocation when it grows: what must be drained first is each call site's own rule.
+template <bool PINNED>
+struct GrowBuf {
     void* p = nullptr;
     size_t cap = 0;
+    static hipError_t free_(void* q) { return PINNED ? hipHostFree(q) : hipFree(q); }
     hipError_t need(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
         if (p) {
-            hipError_t e = hipFree(p);
+            hipError_t e = free_(p);
             if (e != hipSuccess) return e;
             p = nullptr;
             cap = 0;
         }
-        hipError_t e = hipMalloc(&p, bytes);
+        hipError_t e = PINNED ? hipHostMalloc(&p, bytes) : hipMalloc(&p, bytes);
         if (e == hipSuccess) cap = bytes;
         return e;
     }
-    template <class T>
-    T* as() const { return (T*)p; }
+    // frees the buffer; the pointer is dropped even if the free fails (nothing is left to free twice)
+    hipError_t release() {
+        hipError_t e = p ? free_(p) : hipSuccess;
+        p = nullptr;
+        cap = 0;
+        return e;
+    }
+    template <class T> T* as() const { return (T*)p; }
 };
+using Buf = GrowBuf<false>;
+using PinnedBuf = GrowBuf<true>;
+// every buffer of a workspace grown to its table's size (bp_layout.h)
+template <size_t N>
+hipError_t need_all(Buf (&b)[N], const size_t (&sz)[N]) {
+    for (size_t i = 0; i < N; i++) {
+        hipError_t e = b[i].need(sz[i]);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 // HIP-event timing of the verify pipeline's kernels (bench.py's live roofline numbers).
 struct EventTimer {
@@ -121,6 +142,27 @@ struct EventTimer {
     }
 };
 
+struct Pipeline;
+
+// Everything the engine keeps for one caller stream (buffer names and sizes: bp_layout.h), built on
+// first use, freed by hipbp_release_stream_workspaces.  The Part-2 calls run asynchronously on the
+// caller's stream: calls on two streams never share a buffer, and batches on two streams overlap.
+struct StreamWs {
+    Buf msm[bp::MB_COUNT];       // canonical MSM / point tree
+    Buf prove[bp::PB_COUNT];     // prover (hipbp_batch_generate_range_proof)
+    // seeded prover (hipbp_batch_generate_range_proof_seeded): the per-proof keys and the derived
+    // scalars of a batch, rnd | sL | sR
+    Buf seed_keys, seed_scal;
+    // stand-alone IPA prover (hipbp_batch_inner_product_prove): two chunk workspaces, the second run
+    // on an internal side stream so one chunk's latency-bound chains run under the other's scalar
+    // multiplications (the Pippenger path's scheme)
+    Buf ipa[2][bp::IB_COUNT];
+    hipStream_t ipa_side = nullptr;
+    hipEvent_t ipa_ev[2] = {};   // [0] the caller's stream at entry, [1] the side stream's last chunk done
+    std::map<std::pair<int, int>, Pipeline*> pipes;   // one-shot verify pipelines, per (n, mode)
+    hipError_t release(hipError_t first);
+};
+
 // Per-device state. The identity-doubling and power-of-two tables are built on first use and cached.
 struct Engine {
     EventTimer timer;
@@ -129,14 +171,29 @@ struct Engine {
     bp::ge* dtab = nullptr;
     bp::fe* two_i = nullptr;
     int two_cap = 0;
-    // single-call staging (Part 1: the engine's own stream, synchronous calls)
-    Buf h2d[8], scratch[8];
+    // single-call staging (Part 1: the engine's own stream, synchronous calls): two operand arrays and
+    // the result of the reference-surface calls, launch_ip_grid's partial sums, and
+    // hipbp_inner_product_prove_host's inputs and outputs
+    Buf op_a, op_b, op_out, ip_part, ipa_stage;
+    // ... of a single-proof verify: the staged proof, G | H | h | P and the verdict.  single_gens: the
+    // G | H | h last uploaded to gens1, as host bytes: a call with the same bytes (the reference's
+    // caller passes one generator set call after call) skips their three pageable copies
+    Buf proof1, gens1, ok1;
+    std::vector<uint8_t> single_gens;
+    const void* single_gens_dev = nullptr;
+    // ... and its pinned host staging (a pageable source of an async copy must outlive the copy; this
+    // one does, and the stream is synced after use): drained of the engine stream's work before it grows
+    PinnedBuf pinned;
+    hipError_t need_pinned(size_t bytes) {
+        hipError_t r;
+        if (bytes > pinned.cap && pinned.p && (r = hipStreamSynchronize(stream)) != hipSuccess) return r;
+        return pinned.need(bytes);
+    }
     // hipbp_batch_range_proof_verify_host: a second stream (chunks alternate over two pipelines)
     // and grow-only staging (pinned host + device), reused across calls
     hipStream_t stream2 = nullptr;
     Buf host_dev;
-    uint8_t* host_pinned = nullptr;
-    size_t host_pinned_cap = 0;
+    PinnedBuf host_pinned;
     // ... and the fixed-base prefix tables of the last generator set it saw (G | H | h, h standing
     // in for g, which cuda_range_proof_verify does not read), kept across calls: a caller verifying
     // batch after batch against one generator set builds them once.  Keyed by the generators' bytes
@@ -145,69 +202,16 @@ struct Engine {
     std::vector<uint8_t> host_gens_key;
     Buf host_gens, host_tab;
     int host_tab_bits = 0;
-    // MSM / point-tree workspaces, one set per stream: the Part-2 calls run asynchronously on
-    // the caller's stream, so two MSMs on two streams (or an async MSM and a Part-1 call on the
-    // engine stream) must never share buffers.  [0] per-point terms, [1..2] block roots,
-    // [3..4] tree ping-pong, [5] lane order, [6] sort bins.
-    struct MsmBufs { Buf b[7]; };
-    std::map<hipStream_t, MsmBufs*> msm_ws;
-    Buf* msm_bufs(hipStream_t s) {
-        MsmBufs*& m = msm_ws[s];
-        if (!m) m = new MsmBufs();
-        return m->b;
-    }
-    // prover workspaces (hipbp_batch_generate_range_proof), one per stream so batches on
-    // different streams overlap (one batch's latency-bound stages under another's term launch)
-    struct ProverBufs {
-        Buf b[19];
-    };
-    std::map<hipStream_t, ProverBufs*> provers;
-    // seeded prover (hipbp_batch_generate_range_proof_seeded): the derived scalars of a batch, rnd | sL |
-    // sR, and the per-proof keys, one set per stream like the prover's own buffers.  seed_mu is held
-    // from the derive launches to the end of the prover's enqueue (taken before `mu`), so two host
-    // threads on one stream cannot interleave a derivation between another's derivation and its prover.
-    struct SeedBufs {
-        Buf keys, scal;
-    };
-    std::map<hipStream_t, SeedBufs*> seed_ws;
-    std::mutex seed_mu;
     // hipbp_batch_generate_range_proof_host: its own staging (pinned host + device, two chunk slots and
     // the generators), grow-only, guarded by prove_host_mu (taken before seed_mu and mu)
     Buf prove_host_dev;
-    uint8_t* prove_host_pinned = nullptr;
-    size_t prove_host_pinned_cap = 0;
+    PinnedBuf prove_host_pinned;
     std::mutex prove_host_mu;
-    // stand-alone IPA prover workspaces (hipbp_batch_inner_product_prove), per caller stream: two
-    // chunk workspaces, the second run on an internal side stream so one chunk's latency-bound
-    // chains run under the other's scalar multiplications (the Pippenger path's scheme)
-    struct IpaBufs {
-        Buf b[2][14];
-        hipStream_t side = nullptr;
-        hipEvent_t ev[2] = {};   // [0] the caller's stream at entry, [1] the side stream's last chunk done
-    };
-    std::map<hipStream_t, IpaBufs*> ipa_ws;
-    // the generators (G | H | h) a single-proof call last uploaded to h2d[4], as host bytes: the next
-    // call with the same bytes (the reference's caller passes one generator set call after call)
-    // skips their three pageable copies
-    std::vector<uint8_t> single_gens;
-    const void* single_gens_dev = nullptr;
-    // pinned host staging for the single-proof entry points (a pageable source of an
-    // async copy must outlive the copy; this one does, and the stream is synced after use)
-    uint8_t* pinned = nullptr;
-    size_t pinned_cap = 0;
-    hipError_t need_pinned(size_t bytes) {
-        if (bytes <= pinned_cap) return hipSuccess;
-        hipError_t r;
-        if (pinned && (r = hipStreamSynchronize(stream)) != hipSuccess) return r;
-        if (pinned && (r = hipHostFree(pinned)) != hipSuccess) return r;
-        pinned = nullptr;
-        pinned_cap = 0;
-        if ((r = hipHostMalloc(&pinned, bytes)) != hipSuccess) return r;
-        pinned_cap = bytes;
-        return hipSuccess;
-    }
-    // one-shot verify pipelines, per (stream, n, mode), so batches on different streams overlap
-    std::map<std::tuple<hipStream_t, int, int>, struct Pipeline*> pipes;
+    // the per-stream workspaces (guarded by mu).  seed_mu is held from the seeded prover's derive
+    // launches to the end of the prover's enqueue (taken before `mu`), so two host threads on one
+    // stream cannot interleave a derivation between another's derivation and its prover.
+    std::map<hipStream_t, StreamWs> streams;
+    std::mutex seed_mu;
     std::mutex mu;
 
     hipError_t init() {
@@ -237,8 +241,8 @@ struct Engine {
         hipError_t e;
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
         if ((e = need_pinned(bytes)) != hipSuccess) return e;
-        memcpy(pinned, src, bytes);
-        bp::launch_upload(dst, pinned, bytes, stream);
+        memcpy(pinned.p, src, bytes);
+        bp::launch_upload(dst, pinned.p, bytes, stream);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         return hipStreamSynchronize(stream);
     }
@@ -297,9 +301,16 @@ Engine& engine_or_exit() {
     return *e;
 }
 
+// How an entry point begins: the current device's engine as `e` (and `err`, for its own HIP calls),
+// or HIPBP_ERR_DEVICE with the runtime's message.
+#define BP_ENGINE_OR_RET(e)           \
+    hipError_t err;                   \
+    Engine* e = engine_or_null(&err); \
+    BP_RET_ON(err)
+
 // Part-2 entry points run on the caller's stream; NULL is the default (null) stream, as for a
 // kernel launch — the stream torch reports as 0 — so work stays ordered with the caller's.
-inline hipStream_t pick(void* s, Engine&) { return (hipStream_t)s; }
+inline hipStream_t pick(void* s) { return (hipStream_t)s; }
 
 bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 
@@ -350,12 +361,21 @@ struct Gens {
     const bp::ge* H() const { return gen.as<bp::ge>() + n; }
     const bp::ge* h() const { return gen.as<bp::ge>() + 2 * n; }
     const bp::ge* g() const { return gen.as<bp::ge>() + 2 * n + 1; }
-    void release() {
-        if (gen.p) (void)hipFree(gen.p);
-        if (tab.p) (void)hipFree(tab.p);
-        gen.p = tab.p = nullptr;
-    }
+    void release() { (void)gen.release(); (void)tab.release(); }
 };
+
+// What every _gens entry point checks of its generator set: that it is there, that it holds the
+// call's n (`what` is the entry point's own message; null: the call brings no n) and that it was
+// created on the current device.
+int gens_check(const void* gens, size_t n, const char* what) {
+    const Gens* gs = (const Gens*)gens;
+    if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
+    if (what && n != gs->n) { g_err = what; return HIPBP_ERR_ARG; }
+    int dev = -1;
+    BP_RET_ON(hipGetDevice(&dev));
+    if (dev != gs->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    return HIPBP_OK;
+}
 
 // Drain-tick thresholds (bp::plan_tick): ticks with at most this many scalar-multiplication items
 // run them on lane quads, up to PAIR_MAX_ITEMS on lane pairs.  The cost model (tools/ubench_issue.hip
@@ -379,11 +399,9 @@ struct Pipeline {
     int n = 0, D = 0;
     int range_mode = 1;   // 0 inner product only, 1 cuda_range_proof_verify, 2 range_proof_verify
     const bp::ge *G = nullptr, *H = nullptr, *g = nullptr, *h = nullptr;
-    // a slot's device buffers: the verify workspace (bp::VerifyWs), its mode-2 part, the lane orders
-    enum { B_SG, B_SH, B_SC, B_U, B_UINV, B_IPOK, B_MSM_PTS, B_MSM_PART, B_TERMS, B_FOLD0, B_FOLD1, B_FIN, B_PIN,
-           B_PSC, B_PTERM, B_LR, B_CHAL, B_M3, B_RFLAGS, B_PERM, B_PBASE, B_COUNT };
+    // a slot's device buffers (bp::VerifyBuf): the verify workspace, its mode-2 part, the lane orders
     struct Slot {
-        Buf b[B_COUNT];
+        Buf b[bp::B_COUNT];
         bp::SlotDev dev{};
         hipEvent_t copied = nullptr;
     };
@@ -408,6 +426,9 @@ struct Pipeline {
     const bp::ge* ext_tab = nullptr;
     int pbits = 0;
     const bp::ge* tables() const { return ext_tab ? ext_tab : ptab.as<bp::ge>(); }
+    void set_gens(const void* G_, const void* H_, const void* g_, const void* h_) {
+        G = (const bp::ge*)G_; H = (const bp::ge*)H_; g = (const bp::ge*)g_; h = (const bp::ge*)h_;
+    }
     hipError_t init(Engine* eng, hipStream_t st, int nn, int range) {
         e = eng; s = st; n = nn; range_mode = range;
         cfg.n = n; cfg.range_mode = range;
@@ -438,14 +459,14 @@ struct Pipeline {
     void release() {
         if (s) (void)hipStreamSynchronize(s);
         for (auto& sl : slots) {
-            for (auto& b : sl.b) if (b.p) (void)hipFree(b.p);
+            for (auto& b : sl.b) (void)b.release();
             if (sl.copied) (void)hipEventDestroy(sl.copied);
         }
         if (slots_dev) (void)hipFree(slots_dev);
         if (host_dev) (void)hipHostFree(host_dev);
-        if (sort_bins.p) (void)hipFree(sort_bins.p);
-        if (sort_offs.p) (void)hipFree(sort_offs.p);
-        if (ptab.p) (void)hipFree(ptab.p);
+        (void)sort_bins.release();
+        (void)sort_offs.release();
+        (void)ptab.release();
     }
     // The batch's lane-order buffers and sort plan (its per-lane item sets: bp::lane_sort_sets).
     hipError_t plan_sort(Slot& sl, int idx) {
@@ -458,14 +479,14 @@ struct Pipeline {
         if (!ss.count) return hipSuccess;
         plan.longest_first = (cfg.lane_sort_mask & 8) ? 0 : 1;
         hipError_t r;
-        if ((r = sl.b[B_PERM].need(ss.total * sizeof(uint32_t))) != hipSuccess) return r;
+        if ((r = sl.b[bp::B_PERM].need(ss.total * sizeof(uint32_t))) != hipSuccess) return r;
         const size_t nb = (size_t)bp::LANE_SORT_SETS * bp::MSM_BINS * sizeof(unsigned);
         if (!sort_bins.p) {
             if ((r = sort_bins.need(nb)) != hipSuccess) return r;
             if ((r = hipMemsetAsync(sort_bins.p, 0, nb, s)) != hipSuccess) return r;
             if ((r = sort_offs.need(nb)) != hipSuccess) return r;
         }
-        uint32_t* base = sl.b[B_PERM].as<uint32_t>();
+        uint32_t* base = sl.b[bp::B_PERM].as<uint32_t>();
         for (int k = 0; k < ss.count; k++) {
             bp::LaneSortPlan::Set& st = plan.set[k];
             st.kind = ss.set[k].kind; st.r = ss.set[k].r; st.items = ss.set[k].items; st.perm = base;
@@ -485,31 +506,14 @@ struct Pipeline {
         return false;
     }
     hipError_t carve(Slot& sl, size_t B, size_t Lb) {
-        hipError_t r;
-        size_t Lc = Lb ? Lb : 1;
-        const size_t sz[B_PSC] = {B * 32, B * n * 32, B * 4 * 32, B * Lc * 32, B * Lc * 32, B, B * 2 * n * 128,
-                                  B * 2 * 128, B * 4 * 128, B * 2 * n * 128, B * 2 * n * 128, B * 2 * 128, B * 128};
-        for (int i = 0; i < B_PSC; i++)
-            if ((r = sl.b[i].need(sz[i])) != hipSuccess) return r;
-        bp::VerifyWs& w = sl.dev.ws;
-        w.sG = sl.b[B_SG].as<bp::fe>(); w.sH = sl.b[B_SH].as<bp::fe>(); w.sc = sl.b[B_SC].as<bp::fe>();
-        w.u = sl.b[B_U].as<bp::fe>(); w.uinv = sl.b[B_UINV].as<bp::fe>(); w.ipok = sl.b[B_IPOK].as<uint8_t>();
-        w.msm_pts = sl.b[B_MSM_PTS].as<bp::ge>(); w.msm_part = sl.b[B_MSM_PART].as<bp::ge>();
-        w.terms = sl.b[B_TERMS].as<bp::ge>();
-        w.fold[0] = sl.b[B_FOLD0].as<bp::ge>(); w.fold[1] = sl.b[B_FOLD1].as<bp::ge>();
-        w.fin = sl.b[B_FIN].as<bp::ge>(); w.Pin = sl.b[B_PIN].as<bp::ge>();
-        if (range_mode == 2) {
-            const size_t sz2[6] = {B * 8 * 32, B * 8 * 128, B * 2 * 128, B * 32, B * 2 * 128, B};
-            for (int i = 0; i < 6; i++)
-                if ((r = sl.b[B_PSC + i].need(sz2[i])) != hipSuccess) return r;
-            if ((r = sl.b[B_PBASE].need(B * 3 * 128)) != hipSuccess) return r;
-            w.psc = sl.b[B_PSC].as<bp::fe>(); w.pterm = sl.b[B_PTERM].as<bp::ge>(); w.lr = sl.b[B_LR].as<bp::ge>();
-            w.chal = sl.b[B_CHAL].as<bp::fe>(); w.m3 = sl.b[B_M3].as<bp::ge>(); w.rflags = sl.b[B_RFLAGS].as<uint8_t>();
-            w.pbase = sl.b[B_PBASE].as<bp::ge>();
-        } else {
-            w.psc = nullptr; w.pterm = nullptr; w.lr = nullptr; w.chal = nullptr; w.m3 = nullptr; w.rflags = nullptr;
-            w.pbase = nullptr;
-        }
+        using namespace bp;   // the table's ids and types
+        size_t sz[B_COUNT];
+        verify_sizes(B, (size_t)n, Lb, range_mode, sz);
+        Buf(&b)[B_COUNT] = sl.b;
+        hipError_t r = need_all(b, sz);
+        if (r != hipSuccess) return r;
+        bp::VerifyWs& w = sl.dev.ws;   // (the mode-2 fields stay null in the other modes: never allocated)
+        BP_VERIFY_BUFS(BP_BUF_FIELD)
         return hipSuccess;
     }
     // One tick; `b` may be null (drain).  Outputs of `b` are written when it completes.
@@ -571,25 +575,46 @@ struct Pipeline {
 // `count` canonical-tree MSMs of n points each on stream s, in s's own workspace.
 hipError_t msm_run(Engine& e, bp::ge* results, const bp::fe* scalars, const bp::ge* points, size_t n, size_t count,
                    hipStream_t s, const bp::ge* ptab = nullptr, int K = 0) {
-    const size_t tot = n * count, nb = count * ((n + 255) / 256);
-    Buf* w = e.msm_bufs(s);
-    hipError_t err;
-    if ((err = w[0].need(tot * sizeof(bp::ge))) != hipSuccess) return err;
-    if ((err = w[1].need(nb * sizeof(bp::ge))) != hipSuccess) return err;
-    if ((err = w[2].need(nb * sizeof(bp::ge))) != hipSuccess) return err;
-    if ((err = w[5].need(tot * sizeof(uint32_t))) != hipSuccess) return err;
-    if ((err = w[6].need(bp::MSM_BINS * sizeof(unsigned))) != hipSuccess) return err;
-    bp::launch_msm_full(results, scalars, points, n, w[0].as<bp::ge>(), w[1].as<bp::ge>(), w[2].as<bp::ge>(),
-                        w[5].as<uint32_t>(), w[6].as<unsigned>(), e.dtab, s, count, ptab, K);
+    Buf(&w)[bp::MB_COUNT] = e.streams[s].msm;
+    size_t sz[bp::MB_COUNT];
+    bp::msm_sizes(n, count, sz);
+    hipError_t err = need_all(w, sz);
+    if (err != hipSuccess) return err;
+    bp::launch_msm_full(results, scalars, points, n, w[bp::MB_TERMS].as<bp::ge>(), w[bp::MB_ROOT0].as<bp::ge>(),
+                        w[bp::MB_ROOT1].as<bp::ge>(), w[bp::MB_ORDER].as<uint32_t>(), w[bp::MB_BINS].as<unsigned>(),
+                        e.dtab, s, count, ptab, K);
     return hipGetLastError();
+}
+
+// Frees everything the stream owns; every pointer is dropped even if a hipFree fails (none is left
+// for a later call to reuse or free twice).  Returns `first`, or the first error met if it had none.
+hipError_t StreamWs::release(hipError_t first) {
+    auto keep = [&first](hipError_t r) { if (first == hipSuccess) first = r; };
+    for (auto& b : msm) keep(b.release());
+    for (auto& b : prove) keep(b.release());
+    keep(seed_keys.release());
+    keep(seed_scal.release());
+    if (ipa_side) keep(hipStreamSynchronize(ipa_side));
+    for (auto& half : ipa)
+        for (auto& b : half) keep(b.release());
+    for (hipEvent_t ev : ipa_ev)
+        if (ev) keep(hipEventDestroy(ev));
+    if (ipa_side) keep(hipStreamDestroy(ipa_side));
+    for (auto& kv : pipes) {
+        kv.second->release();
+        delete kv.second;
+    }
+    pipes.clear();
+    return first;
 }
 
 // The engine's cached one-shot pipeline for (stream, n, mode); created on first use.  Cached only
 // once fully initialised (a failed init is released, never reused).
 int pipeline_for(Engine& e, hipStream_t s, size_t max_batch, int n, int range_mode, Pipeline** out) {
-    auto key = std::make_tuple(s, n, range_mode);
-    auto it = e.pipes.find(key);
-    if (it != e.pipes.end()) {
+    auto& pipes = e.streams[s].pipes;
+    auto key = std::make_pair(n, range_mode);
+    auto it = pipes.find(key);
+    if (it != pipes.end()) {
         *out = it->second;
         return HIPBP_OK;
     }
@@ -600,7 +625,7 @@ int pipeline_for(Engine& e, hipStream_t s, size_t max_batch, int n, int range_mo
         delete pl;
         BP_RET_ON(ierr);
     }
-    e.pipes[key] = pl;
+    pipes[key] = pl;
     *out = pl;
     return HIPBP_OK;
 }
@@ -615,10 +640,7 @@ int run_verify(Engine& e, const hipbp_proof_batch* batch, const ge25519* P_in, c
     if (range_mode) BP_RET_ON(e.ensure_two((int)batch->n));
     Pipeline* pl = nullptr;
     if ((rc = pipeline_for(e, s, batch->count, (int)batch->n, range_mode, &pl)) != HIPBP_OK) return rc;
-    pl->G = (const bp::ge*)G;
-    pl->H = (const bp::ge*)H;
-    pl->h = (const bp::ge*)h;
-    pl->g = (const bp::ge*)g;
+    pl->set_gens(G, H, g, h);
     // a generator set's prefix tables, lent for this call only (the cached pipeline is shared with
     // the calls that have none): the ticks' slot records take the pointer at push
     pl->ext_tab = tab_bits ? tab : nullptr;
@@ -649,19 +671,15 @@ int hipbp_device_count(void) {
 }
 
 int hipbp_sync(void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
-    BP_RET_ON(hipStreamSynchronize(pick(stream, *e)));
+    BP_ENGINE_OR_RET(e);
+    BP_RET_ON(hipStreamSynchronize(pick(stream)));
     return HIPBP_OK;
 }
 
 static const char* kKernelNames[bp::KT_COUNT] = {"k_prep", "k_terms", "k_tree", "k_combine"};
 
 int hipbp_timing_enable(int on) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     std::lock_guard<std::mutex> lk(e->mu);
     BP_RET_ON(e->timer.collect());
     e->timer.reset();
@@ -670,9 +688,7 @@ int hipbp_timing_enable(int on) {
 }
 
 int hipbp_timing_collect(double* total_ms, uint64_t* launches) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     std::lock_guard<std::mutex> lk(e->mu);
     BP_RET_ON(e->timer.collect());
     for (int i = 0; i < bp::KT_COUNT; i++) {
@@ -690,25 +706,21 @@ int hipbp_batch_range_proof_verify(const hipbp_proof_batch* batch, const ge25519
                                    const ge25519* g, const ge25519* h, uint8_t* ok, ge25519* P_out,
                                    ge25519* check_out, void* stream) {
     (void)g;   // g is not read by cuda_range_proof_verify (crv:82-127)
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (batch && batch->count == 0) return HIPBP_OK;   // nothing read or written: empty outputs may be null
     if (!G || !H || !h || !ok) { g_err = "null generator/output"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    return run_verify(*e, batch, nullptr, G, H, h, ok, P_out, check_out, 1, pick(stream, *e));
+    return run_verify(*e, batch, nullptr, G, H, h, ok, P_out, check_out, 1, pick(stream));
 }
 
 int hipbp_batch_range_proof_verify_std(const hipbp_proof_batch* batch, const ge25519* G, const ge25519* H,
                                        const ge25519* g, const ge25519* h, uint8_t* ok, ge25519* P_out,
                                        ge25519* check_out, uint8_t* flags_out, ge25519* poly_out, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (batch && batch->count == 0) return HIPBP_OK;   // nothing read or written: empty outputs may be null
     if (!G || !H || !g || !h || !ok) { g_err = "null generator/output"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    return run_verify(*e, batch, nullptr, G, H, h, ok, P_out, check_out, 2, pick(stream, *e), g, flags_out,
+    return run_verify(*e, batch, nullptr, G, H, h, ok, P_out, check_out, 2, pick(stream), g, flags_out,
                       poly_out);
 }
 
@@ -716,29 +728,25 @@ int hipbp_batch_range_proof_verify_gens(const hipbp_proof_batch* batch, void* ge
                                         ge25519* check_out, void* stream) {
     Gens* gs = (Gens*)gens;
     if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (batch && batch->count == 0) return HIPBP_OK;   // nothing read or written: empty outputs may be null
     if (!ok) { g_err = "null output"; return HIPBP_ERR_ARG; }
-    if (batch && batch->n != gs->n) { g_err = "batch n differs from the generator set's"; return HIPBP_ERR_ARG; }
-    if (gs->device != e->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    if (int rc = gens_check(gs, batch ? batch->n : 0, batch ? "batch n differs from the generator set's" : nullptr))
+        return rc;
     std::lock_guard<std::mutex> lk(e->mu);
     return run_verify(*e, batch, nullptr, (const ge25519*)gs->G(), (const ge25519*)gs->H(), (const ge25519*)gs->h(),
-                      ok, P_out, check_out, 1, pick(stream, *e), nullptr, nullptr, nullptr,
+                      ok, P_out, check_out, 1, pick(stream), nullptr, nullptr, nullptr,
                       gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits);
 }
 
 int hipbp_batch_inner_product_verify(const hipbp_proof_batch* batch, const ge25519* P, const ge25519* G,
                                      const ge25519* H, const ge25519* Q, uint8_t* ok, ge25519* check_out,
                                      void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (batch && batch->count == 0) return HIPBP_OK;   // nothing read or written: empty outputs may be null
     if (!P || !G || !H || !Q || !ok) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    return run_verify(*e, batch, P, G, H, Q, ok, nullptr, check_out, 0, pick(stream, *e));
+    return run_verify(*e, batch, P, G, H, Q, ok, nullptr, check_out, 0, pick(stream));
 }
 
 void* hipbp_pipeline_create(size_t max_batch, size_t n, int range_mode, const ge25519* G, const ge25519* H,
@@ -756,17 +764,14 @@ void* hipbp_pipeline_create(size_t max_batch, size_t n, int range_mode, const ge
         }
     }
     Pipeline* pl = new Pipeline();
-    err = pl->init(e, pick(stream, *e), (int)n, range_mode);
+    err = pl->init(e, pick(stream), (int)n, range_mode);
     if (err != hipSuccess) {
         g_err = std::string("pipeline init: ") + hipGetErrorString(err);
         pl->release();
         delete pl;
         return nullptr;
     }
-    pl->G = (const bp::ge*)G;
-    pl->H = (const bp::ge*)H;
-    pl->h = (const bp::ge*)h;
-    pl->g = (const bp::ge*)g;
+    pl->set_gens(G, H, g, h);
     return pl;
 }
 
@@ -795,11 +800,7 @@ int hipbp_pipeline_prefix_tables(void* handle, int bits) {
     BP_RET_ON(hipStreamSynchronize(pl->s));
     pl->pbits = 0;
     pl->ext_tab = nullptr;
-    if (pl->ptab.p) {
-        BP_RET_ON(hipFree(pl->ptab.p));
-        pl->ptab.p = nullptr;
-        pl->ptab.cap = 0;
-    }
+    BP_RET_ON(pl->ptab.release());
     if (!bits) return HIPBP_OK;
     const size_t bytes = ((size_t)(2 * pl->n + 2) << bits) * sizeof(bp::ge);
     BP_RET_ON(pl->ptab.need(bytes));
@@ -820,47 +821,38 @@ void hipbp_pipeline_destroy(void* handle) {
 }
 
 int hipbp_msm(ge25519* result, const fe25519* scalars, const ge25519* points, size_t n, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (n == 0) return HIPBP_OK;
     if (!result || !scalars || !points) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = pick(stream, *e);
-    BP_RET_ON(msm_run(*e, (bp::ge*)result, (const bp::fe*)scalars, (const bp::ge*)points, n, 1, s));
+    BP_RET_ON(msm_run(*e, (bp::ge*)result, (const bp::fe*)scalars, (const bp::ge*)points, n, 1, pick(stream)));
     BP_RET_ON(hipGetLastError());
     return HIPBP_OK;
 }
 
 int hipbp_msm_batch(ge25519* results, const fe25519* scalars, const ge25519* points, size_t n, size_t count,
                     void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (n == 0 || count == 0) return HIPBP_OK;
     if (!results || !scalars || !points) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     if (count > 0x7FFFFFFFull || n * count > 0xFFFFFFFFull) { g_err = "msm_batch: too many items"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = pick(stream, *e);
-    BP_RET_ON(msm_run(*e, (bp::ge*)results, (const bp::fe*)scalars, (const bp::ge*)points, n, count, s));
+    BP_RET_ON(msm_run(*e, (bp::ge*)results, (const bp::fe*)scalars, (const bp::ge*)points, n, count, pick(stream)));
     BP_RET_ON(hipGetLastError());
     return HIPBP_OK;
 }
 
 int hipbp_msm_batch_gens(ge25519* results, const fe25519* scalars, const void* gens, size_t count, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     const Gens* gs = (const Gens*)gens;
     if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
     if (count == 0 || gs->n == 0) return HIPBP_OK;
     if (!results || !scalars) { g_err = "null argument"; return HIPBP_ERR_ARG; }
-    if (gs->device != e->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    if (int rc = gens_check(gs, 0, nullptr)) return rc;
     const size_t n = 2 * gs->n;
     if (count > 0x7FFFFFFFull || n * count > 0xFFFFFFFFull) { g_err = "msm_batch_gens: too many items"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = pick(stream, *e);
-    BP_RET_ON(msm_run(*e, (bp::ge*)results, (const bp::fe*)scalars, gs->G(), n, count, s,
+    BP_RET_ON(msm_run(*e, (bp::ge*)results, (const bp::fe*)scalars, gs->G(), n, count, pick(stream),
                       gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits));
     BP_RET_ON(hipGetLastError());
     return HIPBP_OK;
@@ -868,9 +860,7 @@ int hipbp_msm_batch_gens(ge25519* results, const fe25519* scalars, const void* g
 
 int hipbp_msm_pippenger_batch(ge25519* results, const fe25519* scalars, const ge25519* points, size_t n,
                               size_t count, int window_bits, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (n == 0 || count == 0) return HIPBP_OK;
     if (!results || !scalars || !points) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     if (window_bits < 4 || window_bits > 12) { g_err = "pippenger: window_bits must be 4..12"; return HIPBP_ERR_ARG; }
@@ -880,7 +870,7 @@ int hipbp_msm_pippenger_batch(ge25519* results, const fe25519* scalars, const ge
     }
     std::lock_guard<std::mutex> lk(e->mu);
     BP_RET_ON(bp::msm_pippenger((bp::ge*)results, (const bp::fe*)scalars, (const bp::ge*)points, n, count, window_bits,
-                                e->dtab, pick(stream, *e)));
+                                e->dtab, pick(stream)));
     return HIPBP_OK;
 }
 
@@ -891,9 +881,7 @@ int hipbp_msm_pippenger(ge25519* result, const fe25519* scalars, const ge25519* 
 
 int hipbp_msm_pippenger_windows(ge25519* window_sums, const fe25519* scalars, const ge25519* points, size_t n,
                                 int window_bits, int w_begin, int w_end, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (window_bits < 4 || window_bits > 12) { g_err = "pippenger: window_bits must be 4..12"; return HIPBP_ERR_ARG; }
     const int W = (256 + window_bits - 1) / window_bits;
     if (w_begin < 0 || w_end > W || w_begin > w_end) { g_err = "pippenger_windows: need 0 <= w_begin <= w_end <= W"; return HIPBP_ERR_ARG; }
@@ -902,7 +890,7 @@ int hipbp_msm_pippenger_windows(ge25519* window_sums, const fe25519* scalars, co
     if (n * (size_t)(w_end - w_begin) > 0x7FFFFFFFull) { g_err = "pippenger: n * windows too large"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
     BP_RET_ON(bp::msm_pippenger_windows((bp::ge*)window_sums, (const bp::fe*)scalars, (const bp::ge*)points, n,
-                                        window_bits, w_begin, w_end, e->dtab, pick(stream, *e)));
+                                        window_bits, w_begin, w_end, e->dtab, pick(stream)));
     return HIPBP_OK;
 }
 
@@ -910,63 +898,18 @@ int hipbp_msm_pippenger_windows(ge25519* window_sums, const fe25519* scalars, co
 // MSM / point-tree buffers, prover buffers, IPA prover pair, one-shot verify pipelines, Pippenger pair),
 // after waiting for the stream.  A later call on that stream builds them again.
 int hipbp_release_stream_workspaces(void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(e->mu);
-    // every cached workspace of s is freed and its map entry removed even if a hipFree fails (no
-    // pointer is left behind for a later call to reuse or free twice); the first error is returned
+    // the stream's record is freed and removed even if a hipFree fails; the first error is returned
     hipError_t first = hipStreamSynchronize(s);
-    auto keep = [&first](hipError_t r) { if (first == hipSuccess) first = r; };
-    auto free_all = [&keep](Buf* bs, size_t nb) {
-        for (size_t i = 0; i < nb; i++)
-            if (bs[i].p) {
-                keep(hipFree(bs[i].p));
-                bs[i].p = nullptr;
-                bs[i].cap = 0;
-            }
-    };
-    auto mi = e->msm_ws.find(s);
-    if (mi != e->msm_ws.end()) {
-        free_all(mi->second->b, sizeof(mi->second->b) / sizeof(mi->second->b[0]));
-        delete mi->second;
-        e->msm_ws.erase(mi);
+    auto it = e->streams.find(s);
+    if (it != e->streams.end()) {
+        first = it->second.release(first);
+        e->streams.erase(it);
     }
-    auto pi = e->provers.find(s);
-    if (pi != e->provers.end()) {
-        free_all(pi->second->b, sizeof(pi->second->b) / sizeof(pi->second->b[0]));
-        delete pi->second;
-        e->provers.erase(pi);
-    }
-    auto si = e->seed_ws.find(s);
-    if (si != e->seed_ws.end()) {
-        free_all(&si->second->keys, 1);
-        free_all(&si->second->scal, 1);
-        delete si->second;
-        e->seed_ws.erase(si);
-    }
-    auto ii = e->ipa_ws.find(s);
-    if (ii != e->ipa_ws.end()) {
-        Engine::IpaBufs* ib = ii->second;
-        if (ib->side) keep(hipStreamSynchronize(ib->side));
-        for (auto& half : ib->b) free_all(half, sizeof(half) / sizeof(half[0]));
-        for (hipEvent_t ev : ib->ev)
-            if (ev) keep(hipEventDestroy(ev));
-        if (ib->side) keep(hipStreamDestroy(ib->side));
-        delete ib;
-        e->ipa_ws.erase(ii);
-    }
-    for (auto it = e->pipes.begin(); it != e->pipes.end();) {
-        if (std::get<0>(it->first) == s) {
-            it->second->release();
-            delete it->second;
-            it = e->pipes.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    keep(bp::pippenger_release(s));
+    const hipError_t pr = bp::pippenger_release(s);
+    if (first == hipSuccess) first = pr;
     if (first != hipSuccess) {
         g_err = std::string("release_stream_workspaces: ") + hipGetErrorString(first);
         return HIPBP_ERR_DEVICE;
@@ -976,24 +919,20 @@ int hipbp_release_stream_workspaces(void* stream) {
 
 int hipbp_msm_pippenger_horner(ge25519* results, const ge25519* window_sums, size_t count, int window_bits,
                                void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (window_bits < 4 || window_bits > 12) { g_err = "pippenger: window_bits must be 4..12"; return HIPBP_ERR_ARG; }
     if (count == 0) return HIPBP_OK;
     if (!results || !window_sums) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     if (count > 0xFFFFu) { g_err = "pippenger_horner: count <= 65535"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
     BP_RET_ON(bp::pippenger_horner((bp::ge*)results, (const bp::ge*)window_sums, count, window_bits,
-                                   pick(stream, *e)));
+                                   pick(stream)));
     return HIPBP_OK;
 }
 
 static int prove_run(const hipbp_prove_input* in, const ge25519* G, const ge25519* H, const ge25519* g,
                      const ge25519* h, const bp::ge* ptab, int pbits, hipbp_proof_out* out, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (!in || !out || !G || !H || !g || !h) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     if (in->count == 0) return HIPBP_OK;
     if (!is_pow2(in->n) || in->n > 128) { g_err = "prover: n must be a power of two <= 128"; return HIPBP_ERR_ARG; }
@@ -1012,29 +951,19 @@ static int prove_run(const hipbp_prove_input* in, const ge25519* G, const ge2551
     bp::ProveOut po{(bp::ge*)out->V, (bp::ge*)out->A, (bp::ge*)out->S, (bp::ge*)out->T1, (bp::ge*)out->T2,
                     (bp::fe*)out->taux, (bp::fe*)out->mu, (bp::fe*)out->t, (bp::fe*)out->c, (bp::fe*)out->x,
                     (bp::fe*)out->a, (bp::fe*)out->b, (bp::ge*)out->L, (bp::ge*)out->R, out->valid};
-    // workspace: prover buffers are the engine's prv[] (reused across calls on the engine's lock)
-    const size_t FE = sizeof(bp::fe), GE = sizeof(bp::ge);
-    const size_t cap = B * (4 * n + 4);
-    size_t sz[17] = {B * 4 * n * FE, cap * GE, B * 4 * GE, B * 5 * GE, B * 8 * FE, B * 4 * FE, B * 4 * GE,
-                     B * n * FE, B * n * FE, B * 2 * n * FE, B * 2 * FE, B * (2 * n + 2) * GE, B * 4 * FE, B,
-                     2 * cap * sizeof(uint32_t), 2 * sizeof(unsigned), 2 * n * GE};
-    hipStream_t s = pick(stream, *e);
-    Engine::ProverBufs*& pb = e->provers[s];
-    if (!pb) pb = new Engine::ProverBufs();
-    Buf* prv = pb->b;
-    // terms0's heavy-list sort (HIPBP_PROVE_SORT=0 turns it off, for A/B runs)
+    // workspace: the stream's prover buffers (reused across calls on the engine's lock)
+    using namespace bp;   // the table's ids and types
+    hipStream_t s = pick(stream);
+    Buf(&b)[PB_COUNT] = e->streams[s].prove;
+    // terms0's heavy-list sort (HIPBP_PROVE_SORT=0 turns it off, for A/B runs: slist, sbins stay null)
     static const bool psort = getenv("HIPBP_PROVE_SORT") ? atoi(getenv("HIPBP_PROVE_SORT")) != 0 : true;
-    const int nbuf = psort ? 19 : 17;
-    size_t sz2[19];
-    for (int i = 0; i < 19; i++) sz2[i] = i < 17 ? sz[i] : 0;
-    if (psort) { sz2[17] = cap * sizeof(uint32_t); sz2[18] = bp::MSM_BINS * sizeof(unsigned); }
-    for (int i = 0; i < nbuf; i++) BP_RET_ON(prv[i].need(sz2[i]));
-    bp::ProveWs w{prv[0].as<bp::fe>(), prv[1].as<bp::ge>(), prv[2].as<bp::ge>(), prv[3].as<bp::ge>(),
-                  prv[4].as<bp::fe>(), prv[5].as<bp::fe>(), prv[6].as<bp::ge>(), prv[7].as<bp::fe>(),
-                  prv[8].as<bp::fe>(), prv[9].as<bp::fe>(), prv[10].as<bp::fe>(), prv[11].as<bp::ge>(),
-                  prv[12].as<bp::fe>(), prv[13].as<uint8_t>(), prv[14].as<uint32_t>(), prv[15].as<unsigned>(), cap,
-                  prv[16].as<bp::ge>(), psort ? prv[17].as<uint32_t>() : nullptr,
-                  psort ? prv[18].as<unsigned>() : nullptr, ptab, ptab ? pbits : 0};
+    size_t sz[PB_COUNT];
+    prove_sizes(B, n, psort, sz);
+    BP_RET_ON(need_all(b, sz));
+    bp::ProveWs w{};
+    BP_PROVE_BUFS(BP_BUF_FIELD)
+    w.cap = prove_cap(B, n);
+    w.ptab = ptab; w.pbits = ptab ? pbits : 0;
     auto run = [&](int stage, int r) {
         bp::launch_prove(stage, r, pin, w, po, (const bp::ge*)G, (const bp::ge*)H, (const bp::ge*)g,
                          (const bp::ge*)h, e->dtab, e->two_i, s);
@@ -1073,7 +1002,7 @@ void* hipbp_gens_create(size_t n, const ge25519* G, const ge25519* H, const ge25
     Gens* gs = new Gens();
     gs->device = e->device;
     gs->n = n;
-    hipStream_t s = pick(stream, *e);
+    hipStream_t s = pick(stream);
     const size_t GE = sizeof(ge25519);
     auto fail = [&](hipError_t er, const char* what) -> void* {
         g_err = std::string(what) + ": " + hipGetErrorString(er);
@@ -1107,12 +1036,8 @@ void hipbp_gens_destroy(void* gens) {
 
 int hipbp_batch_generate_range_proof_gens(const hipbp_prove_input* in, void* gens, hipbp_proof_out* out,
                                           void* stream) {
-    Gens* gs = (Gens*)gens;
-    if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
-    if (!in || in->n != gs->n) { g_err = "prover: input n differs from the generator set's"; return HIPBP_ERR_ARG; }
-    int dev = -1;
-    BP_RET_ON(hipGetDevice(&dev));
-    if (dev != gs->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    Gens* gs = (Gens*)gens;   // (a set's n is never 0: a null `in` fails the n check)
+    if (int rc = gens_check(gs, in ? in->n : 0, "prover: input n differs from the generator set's")) return rc;
     return prove_run(in, (const ge25519*)gs->G(), (const ge25519*)gs->H(), (const ge25519*)gs->g(),
                      (const ge25519*)gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits, out, stream);
 }
@@ -1129,29 +1054,25 @@ static int seed_check(const uint8_t* seed32, const fe25519* v, const fe25519* ga
 }
 
 // the key workspace of stream s (e.mu held by the caller), grown to B keys
-static int seed_keys(Engine& e, hipStream_t s, size_t B, Engine::SeedBufs** out) {
-    Engine::SeedBufs*& sb = e.seed_ws[s];
-    if (!sb) sb = new Engine::SeedBufs();
-    BP_RET_ON(sb->keys.need(B * sizeof(bp::fe)));
-    *out = sb;
+static int seed_keys(Engine& e, hipStream_t s, size_t B, StreamWs** out) {
+    *out = &e.streams[s];
+    BP_RET_ON((*out)->seed_keys.need(B * sizeof(bp::fe)));
     return HIPBP_OK;
 }
 
 int hipbp_derive_prover_scalars(const uint8_t* seed32, const fe25519* v, const fe25519* gamma, uint64_t index_base,
                                 size_t count, size_t n, fe25519* sL, fe25519* sR, fe25519* rnd, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     int rc = seed_check(seed32, v, gamma, count, n);
     if (rc != HIPBP_OK) return rc;
     if (!sL || !sR || !rnd) { g_err = "derive: null output"; return HIPBP_ERR_ARG; }
     if (count == 0) return HIPBP_OK;
-    hipStream_t s = pick(stream, *e);
+    hipStream_t s = pick(stream);
     std::lock_guard<std::mutex> lk(e->mu);
-    Engine::SeedBufs* sb = nullptr;
+    StreamWs* sb = nullptr;
     if ((rc = seed_keys(*e, s, count, &sb)) != HIPBP_OK) return rc;
     bp::launch_seed_derive(bp::seed_words(seed32), (const bp::fe*)v, (const bp::fe*)gamma, index_base, (uint32_t)count,
-                           (uint32_t)n, sb->keys.as<bp::fe>(), (bp::fe*)sL, (bp::fe*)sR, (bp::fe*)rnd, s);
+                           (uint32_t)n, sb->seed_keys.as<bp::fe>(), (bp::fe*)sL, (bp::fe*)sR, (bp::fe*)rnd, s);
     BP_RET_ON(hipGetLastError());
     return HIPBP_OK;
 }
@@ -1159,9 +1080,7 @@ int hipbp_derive_prover_scalars(const uint8_t* seed32, const fe25519* v, const f
 static int prove_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base, const ge25519* G,
                         const ge25519* H, const ge25519* g, const ge25519* h, const bp::ge* ptab, int pbits,
                         hipbp_proof_out* out, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (!in || !out || !G || !H || !g || !h) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     if (in->sL || in->sR || in->rnd) {
         g_err = "seeded prover: sL, sR and rnd must be NULL (the scalars are derived from the seed)";
@@ -1171,17 +1090,17 @@ static int prove_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint
     if (rc != HIPBP_OK) return rc;
     if (in->count == 0) return HIPBP_OK;
     const size_t B = in->count, n = in->n;
-    hipStream_t s = pick(stream, *e);
+    hipStream_t s = pick(stream);
     std::lock_guard<std::mutex> slk(e->seed_mu);
     bp::fe* scal = nullptr;
     {
         std::lock_guard<std::mutex> lk(e->mu);
-        Engine::SeedBufs* sb = nullptr;
+        StreamWs* sb = nullptr;
         if ((rc = seed_keys(*e, s, B, &sb)) != HIPBP_OK) return rc;
-        BP_RET_ON(sb->scal.need(B * (2 * n + 4) * sizeof(bp::fe)));   // rnd [B*4] | sL [B*n] | sR [B*n]
-        scal = sb->scal.as<bp::fe>();
+        BP_RET_ON(sb->seed_scal.need(B * (2 * n + 4) * sizeof(bp::fe)));   // rnd [B*4] | sL [B*n] | sR [B*n]
+        scal = sb->seed_scal.as<bp::fe>();
         bp::launch_seed_derive(bp::seed_words(seed32), (const bp::fe*)in->v, (const bp::fe*)in->gamma, index_base,
-                               (uint32_t)B, (uint32_t)n, sb->keys.as<bp::fe>(), scal + 4 * B, scal + (4 + n) * B, scal,
+                               (uint32_t)B, (uint32_t)n, sb->seed_keys.as<bp::fe>(), scal + 4 * B, scal + (4 + n) * B, scal,
                                s);
         BP_RET_ON(hipGetLastError());
     }
@@ -1201,11 +1120,7 @@ int hipbp_batch_generate_range_proof_seeded(const hipbp_prove_input* in, const u
 int hipbp_batch_generate_range_proof_seeded_gens(const hipbp_prove_input* in, const uint8_t* seed32,
                                                  uint64_t index_base, void* gens, hipbp_proof_out* out, void* stream) {
     Gens* gs = (Gens*)gens;
-    if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
-    if (!in || in->n != gs->n) { g_err = "prover: input n differs from the generator set's"; return HIPBP_ERR_ARG; }
-    int dev = -1;
-    BP_RET_ON(hipGetDevice(&dev));
-    if (dev != gs->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    if (int rc = gens_check(gs, in ? in->n : 0, "prover: input n differs from the generator set's")) return rc;
     return prove_seeded(in, seed32, index_base, (const ge25519*)gs->G(), (const ge25519*)gs->H(),
                         (const ge25519*)gs->g(), (const ge25519*)gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr,
                         gs->bits, out, stream);
@@ -1228,16 +1143,14 @@ int hipbp_batch_generate_range_proof_host(RangeProof* proofs, uint8_t* valid, co
     int rc = seed_check(seed32, v, gamma, 0, n);
     if (rc != HIPBP_OK) return rc;
     if (G->length != n || H->length != n) { g_err = "prover: G and H must hold n generators"; return HIPBP_ERR_ARG; }
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     size_t CH = 16384;
     if (const char* ce = getenv("HIPBP_PROVE_HOST_CHUNK"))
         if (atol(ce) > 0) CH = std::min<size_t>((size_t)atol(ce), (size_t)1 << 22);
     CH = std::min(CH, count);
-    const size_t GE = sizeof(ge25519), FE = sizeof(fe25519), Lr = (size_t)log2i(n);
-    const size_t o_pts = 2 * CH * FE, o_fe = o_pts + 5 * CH * GE, o_lr = o_fe + 7 * CH * FE;
-    const size_t o_valid = o_lr + 2 * CH * Lr * GE, slot_bytes = (o_valid + CH + 127) & ~(size_t)127;
+    const size_t GE = bp::GE, FE = bp::FE, Lr = (size_t)log2i(n);
+    // a slot: v | gamma [CH], then the proof-output layout (bp::OutLayout)
+    const size_t slot_bytes = bp::OutLayout{CH, CH, Lr, 2 * CH * FE}.slot_bytes();
     const size_t gen_off = 2 * slot_bytes, bytes = gen_off + (2 * n + 2) * GE;
     memset(proofs, 0, count * sizeof(RangeProof));
     memset(valid, 0, count);
@@ -1251,17 +1164,9 @@ int hipbp_batch_generate_range_proof_host(RangeProof* proofs, uint8_t* valid, co
     }
     // (calls of this function serialise on prove_host_mu and each ends with both streams drained
     // of its work, so nothing still reads the staging when it grows)
-    if (bytes > e->prove_host_pinned_cap) {
-        if (e->prove_host_pinned) {
-            BP_RET_ON(hipHostFree(e->prove_host_pinned));
-            e->prove_host_pinned = nullptr;
-            e->prove_host_pinned_cap = 0;
-        }
-        BP_RET_ON(hipHostMalloc((void**)&e->prove_host_pinned, bytes));
-        e->prove_host_pinned_cap = bytes;
-    }
+    BP_RET_ON(e->prove_host_pinned.need(bytes));
     BP_RET_ON(e->prove_host_dev.need(bytes));
-    uint8_t* host = e->prove_host_pinned;
+    uint8_t* host = e->prove_host_pinned.as<uint8_t>();
     uint8_t* dbuf = e->prove_host_dev.as<uint8_t>();
     memcpy(host + gen_off, G->elements, n * GE);
     memcpy(host + gen_off + n * GE, H->elements, n * GE);
@@ -1287,34 +1192,12 @@ int hipbp_batch_generate_range_proof_host(RangeProof* proofs, uint8_t* valid, co
     };
     // chunk [c0, c0 + c) out of its slot's pinned staging into the caller's structs
     auto unpack = [&](size_t c0, size_t c, const uint8_t* hs) -> bool {
-        const ge25519* pts = (const ge25519*)(hs + o_pts);
-        const fe25519* f = (const fe25519*)(hs + o_fe);
-        const ge25519* lr = (const ge25519*)(hs + o_lr);
-        const uint8_t* vd = hs + o_valid;
+        const bp::OutLayout lay{CH, c, Lr, 2 * CH * FE};
         for (size_t k = 0; k < c; k++) {
-            RangeProof& p = proofs[c0 + k];
-            p.V = pts[k]; p.A = pts[c + k]; p.S = pts[2 * c + k]; p.T1 = pts[3 * c + k]; p.T2 = pts[4 * c + k];
-            p.taux = f[k]; p.mu = f[c + k]; p.t = f[2 * c + k];
             filled = c0 + k + 1;
-            valid[c0 + k] = vd[k] ? 1 : 0;
-            if (!vd[k]) continue;   // the zeroed proof: ip_proof stays all zero
-            InnerProductProof& ip = p.ip_proof;
-            ip.a.elements = (fe25519*)malloc(FE);
-            ip.b.elements = (fe25519*)malloc(FE);
-            ip.L.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
-            ip.R.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
-            if (!ip.a.elements || !ip.b.elements || !ip.L.elements || !ip.R.elements) return false;
-            ip.n = n;
-            ip.c = f[3 * c + k];
-            ip.x = f[4 * c + k];
-            *ip.a.elements = f[5 * c + k];
-            *ip.b.elements = f[6 * c + k];
-            ip.a.length = ip.b.length = 1;
-            if (Lr) {
-                memcpy(ip.L.elements, lr + k * Lr, Lr * GE);
-                memcpy(ip.R.elements, lr + (c + k) * Lr, Lr * GE);
-            }
-            ip.L.length = ip.R.length = ip.L_len = Lr;
+            const int v = lay.unpack(hs, k, n, proofs[c0 + k]);
+            if (v < 0) return false;
+            valid[c0 + k] = (uint8_t)v;
         }
         return true;
     };
@@ -1357,18 +1240,15 @@ int hipbp_batch_generate_range_proof_host(RangeProof* proofs, uint8_t* valid, co
             what = std::string("chunk H2D: ") + hipGetErrorString(err);
             break;
         }
-        ge25519* dp = (ge25519*)(ds + o_pts);
-        fe25519* df = (fe25519*)(ds + o_fe);
-        ge25519* dl = (ge25519*)(ds + o_lr);
+        const bp::OutLayout lay{CH, c, Lr, 2 * CH * FE};
         hipbp_prove_input in{c, n, (const fe25519*)ds, (const fe25519*)ds + c, nullptr, nullptr, nullptr};
-        hipbp_proof_out out{dp, dp + c, dp + 2 * c, dp + 3 * c, dp + 4 * c,
-                            df, df + c, df + 2 * c, df + 3 * c, df + 4 * c, df + 5 * c, df + 6 * c,
-                            Lr ? dl : nullptr, Lr ? dl + c * Lr : nullptr, ds + o_valid};
+        hipbp_proof_out out;
+        lay.view(ds, &out);
         rc = prove_seeded(&in, seed32, index_base + c0, dG, dG + n, dG + 2 * n, dG + 2 * n + 1, nullptr, 0, &out, st[k]);
         if (rc != HIPBP_OK) { what = g_err; break; }
         // one D2H of the slot's output regions, points .. valid[c) (the regions are sized for a full
         // chunk; a short last chunk's arrays sit packed at the front of each)
-        if ((err = hipMemcpyAsync(hs + o_pts, ds + o_pts, o_valid + c - o_pts, hipMemcpyDeviceToHost, st[k])) != hipSuccess) {
+        if ((err = hipMemcpyAsync(hs + lay.o_pts(), ds + lay.o_pts(), lay.used(), hipMemcpyDeviceToHost, st[k])) != hipSuccess) {
             rc = HIPBP_ERR_DEVICE;
             what = std::string("chunk D2H: ") + hipGetErrorString(err);
         }
@@ -1388,9 +1268,8 @@ static int ipa_enqueue(Engine& e, const hipbp_ipa_prove_input* in, const bp::ge*
                        const bp::ge* ptab, int pbits, const hipbp_ipa_proof_out* out, hipStream_t s) {
     const size_t B = in->count, n = in->n;
     const int Lr = log2i(n);
-    const size_t FE = sizeof(bp::fe), GE = sizeof(bp::ge), cap = 2 * n + 2;
-    // per proof: a, b, prod [n], sc [2n], csc [2], tr, uu [2], x | term [2n], cq [2], chain [4] | slist, llist [cap]
-    const size_t per_proof = (5 * n + 6) * FE + (2 * n + 6) * GE + 2 * cap * sizeof(uint32_t);
+    using namespace bp;   // the IpaBuf names
+    const size_t cap = ipa_cap(n), per_proof = ipa_per_proof(n);
     const char* env = getenv("HIPBP_IPA_WS_MB");
     size_t mb = env ? (size_t)atoll(env) : 512;
     if (mb < 1) mb = 1;
@@ -1398,20 +1277,17 @@ static int ipa_enqueue(Engine& e, const hipbp_ipa_prove_input* in, const bp::ge*
     bmax = std::min(bmax, (size_t)0x7FFFFFFF / cap);   // item ids are 32-bit
     const size_t chunks = std::max((B + bmax - 1) / bmax, std::min<size_t>(B, 2));
     const size_t Bc = (B + chunks - 1) / chunks;
-    Engine::IpaBufs*& ib = e.ipa_ws[s];
-    if (!ib) ib = new Engine::IpaBufs();
-    if (chunks > 1 && !ib->side) {
-        BP_RET_ON(hipStreamCreateWithFlags(&ib->side, hipStreamNonBlocking));
-        for (auto& ev : ib->ev) BP_RET_ON(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    StreamWs* ib = &e.streams[s];
+    if (chunks > 1 && !ib->ipa_side) {
+        BP_RET_ON(hipStreamCreateWithFlags(&ib->ipa_side, hipStreamNonBlocking));
+        for (auto& ev : ib->ipa_ev) BP_RET_ON(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    const size_t sz[14] = {Bc * n * FE, Bc * n * FE, Bc * n * FE, Bc * 2 * n * FE, Bc * 2 * FE, Bc * 2 * n * GE,
-                           Bc * 2 * GE, Bc * 4 * GE, Bc * FE, Bc * 2 * FE, Bc * FE, Bc * cap * sizeof(uint32_t),
-                           Bc * cap * sizeof(uint32_t), (bp::MSM_BINS + 2) * sizeof(unsigned)};
-    for (size_t w = 0; w < std::min<size_t>(chunks, 2); w++)
-        for (int i = 0; i < 14; i++) BP_RET_ON(ib->b[w][i].need(sz[i]));
+    size_t sz[IB_COUNT];
+    ipa_sizes(Bc, n, sz);
+    for (size_t w = 0; w < std::min<size_t>(chunks, 2); w++) BP_RET_ON(need_all(ib->ipa[w], sz));
     if (chunks > 1) {   // the side stream starts after the caller's queued work (the inputs' producers)
-        BP_RET_ON(hipEventRecord(ib->ev[0], s));
-        BP_RET_ON(hipStreamWaitEvent(ib->side, ib->ev[0], 0));
+        BP_RET_ON(hipEventRecord(ib->ipa_ev[0], s));
+        BP_RET_ON(hipStreamWaitEvent(ib->ipa_side, ib->ipa_ev[0], 0));
     }
     const bp::fe *ia = (const bp::fe*)in->a, *ibv = (const bp::fe*)in->b, *ic = (const bp::fe*)in->c,
                  *itr = (const bp::fe*)in->transcript;
@@ -1419,22 +1295,23 @@ static int ipa_enqueue(Engine& e, const hipbp_ipa_prove_input* in, const bp::ge*
         const size_t p0 = c * Bc;
         if (p0 >= B) break;
         const size_t bc = std::min(Bc, B - p0);
-        Buf* w = ib->b[c & 1];
-        hipStream_t st = (c & 1) ? ib->side : s;
-        bp::IpaWs ws{(int)bc, (int)n, Lr, w[0].as<bp::fe>(), w[1].as<bp::fe>(), w[2].as<bp::fe>(), w[3].as<bp::fe>(),
-                     w[4].as<bp::fe>(), w[5].as<bp::ge>(), w[6].as<bp::ge>(), w[7].as<bp::ge>(), w[8].as<bp::fe>(),
-                     w[9].as<bp::fe>(), w[10].as<bp::fe>(), w[11].as<uint32_t>(), w[12].as<uint32_t>(),
-                     w[13].as<unsigned>(), Lr ? (bp::ge*)out->L + p0 * Lr : nullptr,
-                     Lr ? (bp::ge*)out->R + p0 * Lr : nullptr, ptab, ptab ? pbits : 0};
-        bp::launch_ipa_load(ws, ia + p0 * n, ibv + p0 * n, itr ? itr + p0 : nullptr, st);
-        for (int r = 0; r < Lr; r++) bp::launch_ipa_round(ws, r, G, H, Q, e.dtab, st);
-        bp::launch_ipa_final(ws, ic + p0, (bp::fe*)out->a + p0, (bp::fe*)out->b + p0, (bp::fe*)out->c + p0,
+        Buf(&b)[IB_COUNT] = ib->ipa[c & 1];
+        hipStream_t st = (c & 1) ? ib->ipa_side : s;
+        bp::IpaWs w{};
+        BP_IPA_BUFS(BP_BUF_FIELD)
+        w.B = (int)bc; w.n = (int)n; w.Lr = Lr;
+        w.L = Lr ? (bp::ge*)out->L + p0 * Lr : nullptr;
+        w.R = Lr ? (bp::ge*)out->R + p0 * Lr : nullptr;
+        w.ptab = ptab; w.pbits = ptab ? pbits : 0;
+        bp::launch_ipa_load(w, ia + p0 * n, ibv + p0 * n, itr ? itr + p0 : nullptr, st);
+        for (int r = 0; r < Lr; r++) bp::launch_ipa_round(w, r, G, H, Q, e.dtab, st);
+        bp::launch_ipa_final(w, ic + p0, (bp::fe*)out->a + p0, (bp::fe*)out->b + p0, (bp::fe*)out->c + p0,
                              (bp::fe*)out->x + p0, out->c_final ? (bp::fe*)out->c_final + p0 : nullptr, st);
         BP_RET_ON(hipGetLastError());
     }
     if (chunks > 1) {
-        BP_RET_ON(hipEventRecord(ib->ev[1], ib->side));
-        BP_RET_ON(hipStreamWaitEvent(s, ib->ev[1], 0));
+        BP_RET_ON(hipEventRecord(ib->ipa_ev[1], ib->ipa_side));
+        BP_RET_ON(hipStreamWaitEvent(s, ib->ipa_ev[1], 0));
     }
     return HIPBP_OK;
 }
@@ -1453,31 +1330,26 @@ static int ipa_check(const hipbp_ipa_prove_input* in, const hipbp_ipa_proof_out*
 
 int hipbp_batch_inner_product_prove(const hipbp_ipa_prove_input* in, const ge25519* G, const ge25519* H,
                                     const ge25519* Q, hipbp_ipa_proof_out* out, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (!G || !H || !Q) { g_err = "ipa prover: null generator"; return HIPBP_ERR_ARG; }
     if (int rc = ipa_check(in, out)) return rc;
     if (in->count == 0) return HIPBP_OK;
     std::lock_guard<std::mutex> lk(e->mu);
     return ipa_enqueue(*e, in, (const bp::ge*)G, (const bp::ge*)H, (const bp::ge*)Q, nullptr, 0, out,
-                       pick(stream, *e));
+                       pick(stream));
 }
 
 int hipbp_batch_inner_product_prove_gens(const hipbp_ipa_prove_input* in, void* gens, hipbp_ipa_proof_out* out,
                                          void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     Gens* gs = (Gens*)gens;
     if (!gs) { g_err = "null gens"; return HIPBP_ERR_ARG; }
     if (int rc = ipa_check(in, out)) return rc;
-    if (in->n != gs->n) { g_err = "ipa prover: input n differs from the generator set's"; return HIPBP_ERR_ARG; }
-    if (gs->device != e->device) { g_err = "gens: created on another device"; return HIPBP_ERR_ARG; }
+    if (int rc = gens_check(gs, in->n, "ipa prover: input n differs from the generator set's")) return rc;
     if (in->count == 0) return HIPBP_OK;
     std::lock_guard<std::mutex> lk(e->mu);
     return ipa_enqueue(*e, in, gs->G(), gs->H(), gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits, out,
-                       pick(stream, *e));
+                       pick(stream));
 }
 
 // inner_product_prove (bulletproof_vectors.cu:277) on the reference's own host structs: its two
@@ -1502,8 +1374,8 @@ int hipbp_inner_product_prove_host(InnerProductProof* proof, const FieldVector* 
     std::lock_guard<std::mutex> lk(e.mu);
     const size_t FE = sizeof(fe25519), GE = sizeof(ge25519), Lr = (size_t)log2i(n);
     // device staging: G | H | Q | L | R (points), then a | b | c | transcript | out a, b, c, x
-    BP_EXIT_ON(e.scratch[4].need((2 * n + 1 + 2 * Lr) * GE + (2 * n + 6) * FE));
-    ge25519* dG = e.scratch[4].as<ge25519>();
+    BP_EXIT_ON(e.ipa_stage.need((2 * n + 1 + 2 * Lr) * GE + (2 * n + 6) * FE));
+    ge25519* dG = e.ipa_stage.as<ge25519>();
     ge25519 *dH = dG + n, *dQ = dH + n, *dL = dQ + 1, *dR = dL + Lr;
     fe25519* da = (fe25519*)(dR + Lr);
     fe25519 *db = da + n, *dc = db + n, *dt = dc + 1, *oa = dt + 1;
@@ -1522,33 +1394,19 @@ int hipbp_inner_product_prove_host(InnerProductProof* proof, const FieldVector* 
         exit(EXIT_FAILURE);
     }
     fe25519 res[4];
-    fe25519* ha = (fe25519*)malloc(FE);
-    fe25519* hb = (fe25519*)malloc(FE);
-    ge25519* hL = (ge25519*)malloc(Lr ? Lr * GE : 1);
-    ge25519* hR = (ge25519*)malloc(Lr ? Lr * GE : 1);
-    if (!ha || !hb || !hL || !hR) {
+    if (!bp::proof_vectors_alloc(*proof, n, Lr)) {
         fprintf(stderr, "Error: Failed to allocate memory for field vector\n");
         exit(1);
     }
     BP_EXIT_ON(hipMemcpyAsync(res, oa, 4 * FE, hipMemcpyDeviceToHost, s));
     if (Lr) {
-        BP_EXIT_ON(hipMemcpyAsync(hL, dL, Lr * GE, hipMemcpyDeviceToHost, s));
-        BP_EXIT_ON(hipMemcpyAsync(hR, dR, Lr * GE, hipMemcpyDeviceToHost, s));
+        BP_EXIT_ON(hipMemcpyAsync(proof->L.elements, dL, Lr * GE, hipMemcpyDeviceToHost, s));
+        BP_EXIT_ON(hipMemcpyAsync(proof->R.elements, dR, Lr * GE, hipMemcpyDeviceToHost, s));
     }
     BP_EXIT_ON(hipStreamSynchronize(s));
-    *ha = res[0];
-    *hb = res[1];
-    proof->n = n;
-    proof->a.elements = ha;
-    proof->a.length = 1;
-    proof->b.elements = hb;
-    proof->b.length = 1;
+    *proof->a.elements = res[0];
+    *proof->b.elements = res[1];
     proof->c = res[2];
-    proof->L.elements = hL;
-    proof->L.length = Lr;
-    proof->R.elements = hR;
-    proof->R.length = Lr;
-    proof->L_len = Lr;
     proof->x = res[3];
     return HIPBP_OK;
 }
@@ -1562,15 +1420,8 @@ int hipbp_pipeline_use_gens(void* handle, void* gens) {
     std::lock_guard<std::mutex> lk(pl->e->mu);
     if (pl->busy()) { g_err = "use_gens: pipeline has batches in flight (flush first)"; return HIPBP_ERR_ARG; }
     BP_RET_ON(hipStreamSynchronize(pl->s));
-    if (pl->ptab.p) {   // its own tables (hipbp_pipeline_prefix_tables) give way to the set's
-        BP_RET_ON(hipFree(pl->ptab.p));
-        pl->ptab.p = nullptr;
-        pl->ptab.cap = 0;
-    }
-    pl->G = gs->G();
-    pl->H = gs->H();
-    pl->h = gs->h();
-    pl->g = gs->g();
+    BP_RET_ON(pl->ptab.release());   // its own tables (hipbp_pipeline_prefix_tables) give way to the set's
+    pl->set_gens(gs->G(), gs->H(), gs->g(), gs->h());
     pl->ext_tab = gs->bits ? gs->tab.as<bp::ge>() : nullptr;
     pl->pbits = gs->bits;
     return HIPBP_OK;
@@ -1590,30 +1441,27 @@ int hipbp_pipeline_defer_msm(void* handle, int on) {
 }
 
 int hipbp_point_tree(ge25519* result, const ge25519* points, size_t n, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (n == 0) return HIPBP_OK;
     if (!result || !points) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    size_t nb = (n + 255) / 256;
-    hipStream_t s = pick(stream, *e);
-    Buf* w = e->msm_bufs(s);
-    BP_RET_ON(w[3].need(nb * sizeof(bp::ge)));
-    BP_RET_ON(w[4].need(nb * sizeof(bp::ge)));
-    bp::launch_tree_full((bp::ge*)result, (const bp::ge*)points, n, w[3].as<bp::ge>(), w[4].as<bp::ge>(), s);
+    hipStream_t s = pick(stream);
+    Buf(&w)[bp::MB_COUNT] = e->streams[s].msm;
+    size_t sz[bp::MB_COUNT];
+    bp::tree_sizes(n, sz);
+    BP_RET_ON(need_all(w, sz));
+    bp::launch_tree_full((bp::ge*)result, (const bp::ge*)points, n, w[bp::MB_TREE0].as<bp::ge>(),
+                         w[bp::MB_TREE1].as<bp::ge>(), s);
     BP_RET_ON(hipGetLastError());
     return HIPBP_OK;
 }
 
 int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_t count, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (op < 0 || op > 20) { g_err = "bad op"; return HIPBP_ERR_ARG; }
     if (!a || (!b && op != 3 && op != 5 && op != 7 && op != 11 && op != 12)) { g_err = "null operand"; return HIPBP_ERR_ARG; }
     if (count == 0) return HIPBP_OK;
-    hipStream_t s = pick(stream, *e);
+    hipStream_t s = pick(stream);
     if (op == 5)
         bp::launch_invert((bp::fe*)r, (const bp::fe*)a, count, s);
     else
@@ -1623,13 +1471,11 @@ int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_
 }
 
 int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     if (kind < 0 || kind > 5) { g_err = "bad sha probe kind"; return HIPBP_ERR_ARG; }
     if (!out || !in) { g_err = "null operand"; return HIPBP_ERR_ARG; }
     if (count == 0) return HIPBP_OK;
-    bp::launch_sha_probe(kind, (bp::fe*)out, (const bp::fe*)in, count, pick(stream, *e));
+    bp::launch_sha_probe(kind, (bp::fe*)out, (const bp::fe*)in, count, pick(stream));
     BP_RET_ON(hipGetLastError());
     return HIPBP_OK;
 }
@@ -1645,13 +1491,13 @@ void cuda_point_vector_multi_scalar_mul(ge25519* result, const FieldVector* scal
     if (n == 0) return;
     Engine& e = engine_or_exit();
     std::lock_guard<std::mutex> lk(e.mu);
-    BP_EXIT_ON(e.h2d[0].need(n * sizeof(fe25519)));
-    BP_EXIT_ON(e.h2d[1].need(n * sizeof(ge25519)));
-    BP_EXIT_ON(e.h2d[2].need(sizeof(ge25519)));
-    BP_EXIT_ON(hipMemcpyAsync(e.h2d[0].p, scalars->elements, n * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
-    BP_EXIT_ON(hipMemcpyAsync(e.h2d[1].p, points->elements, n * sizeof(ge25519), hipMemcpyHostToDevice, e.stream));
-    BP_EXIT_ON(msm_run(e, e.h2d[2].as<bp::ge>(), e.h2d[0].as<bp::fe>(), e.h2d[1].as<bp::ge>(), n, 1, e.stream));
-    BP_EXIT_ON(hipMemcpyAsync(result, e.h2d[2].p, sizeof(ge25519), hipMemcpyDeviceToHost, e.stream));
+    BP_EXIT_ON(e.op_a.need(n * sizeof(fe25519)));
+    BP_EXIT_ON(e.op_b.need(n * sizeof(ge25519)));
+    BP_EXIT_ON(e.op_out.need(sizeof(ge25519)));
+    BP_EXIT_ON(hipMemcpyAsync(e.op_a.p, scalars->elements, n * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
+    BP_EXIT_ON(hipMemcpyAsync(e.op_b.p, points->elements, n * sizeof(ge25519), hipMemcpyHostToDevice, e.stream));
+    BP_EXIT_ON(msm_run(e, e.op_out.as<bp::ge>(), e.op_a.as<bp::fe>(), e.op_b.as<bp::ge>(), n, 1, e.stream));
+    BP_EXIT_ON(hipMemcpyAsync(result, e.op_out.p, sizeof(ge25519), hipMemcpyDeviceToHost, e.stream));
     BP_EXIT_ON(hipStreamSynchronize(e.stream));
 }
 
@@ -1671,19 +1517,19 @@ static void ip_common(fe25519* result, const FieldVector* a, const FieldVector* 
     if (n == 0) return;
     Engine& e = engine_or_exit();
     std::lock_guard<std::mutex> lk(e.mu);
-    BP_EXIT_ON(e.h2d[0].need(n * sizeof(fe25519)));
-    BP_EXIT_ON(e.h2d[1].need(n * sizeof(fe25519)));
-    BP_EXIT_ON(e.h2d[2].need(sizeof(fe25519)));
-    BP_EXIT_ON(e.scratch[3].need(1024 * sizeof(fe25519)));
-    BP_EXIT_ON(hipMemcpyAsync(e.h2d[0].p, a->elements, n * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
-    BP_EXIT_ON(hipMemcpyAsync(e.h2d[1].p, b->elements, n * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
+    BP_EXIT_ON(e.op_a.need(n * sizeof(fe25519)));
+    BP_EXIT_ON(e.op_b.need(n * sizeof(fe25519)));
+    BP_EXIT_ON(e.op_out.need(sizeof(fe25519)));
+    BP_EXIT_ON(e.ip_part.need(1024 * sizeof(fe25519)));
+    BP_EXIT_ON(hipMemcpyAsync(e.op_a.p, a->elements, n * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
+    BP_EXIT_ON(hipMemcpyAsync(e.op_b.p, b->elements, n * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
     if (force_shared || n <= 512)
-        bp::launch_ip_shared(e.h2d[2].as<bp::fe>(), e.h2d[0].as<bp::fe>(), e.h2d[1].as<bp::fe>(), n, e.stream);
+        bp::launch_ip_shared(e.op_out.as<bp::fe>(), e.op_a.as<bp::fe>(), e.op_b.as<bp::fe>(), n, e.stream);
     else
-        bp::launch_ip_grid(e.h2d[2].as<bp::fe>(), e.scratch[3].as<bp::fe>(), e.h2d[0].as<bp::fe>(),
-                           e.h2d[1].as<bp::fe>(), n, e.stream);
+        bp::launch_ip_grid(e.op_out.as<bp::fe>(), e.ip_part.as<bp::fe>(), e.op_a.as<bp::fe>(),
+                           e.op_b.as<bp::fe>(), n, e.stream);
     BP_EXIT_ON(hipGetLastError());
-    BP_EXIT_ON(hipMemcpyAsync(result, e.h2d[2].p, sizeof(fe25519), hipMemcpyDeviceToHost, e.stream));
+    BP_EXIT_ON(hipMemcpyAsync(result, e.op_out.p, sizeof(fe25519), hipMemcpyDeviceToHost, e.stream));
     BP_EXIT_ON(hipStreamSynchronize(e.stream));
 }
 
@@ -1702,18 +1548,18 @@ void cuda_batch_field_vector_inner_product(fe25519* results, const FieldVector* 
     Engine& e = engine_or_exit();
     std::lock_guard<std::mutex> lk(e.mu);
     size_t tot = num_vectors * n;
-    BP_EXIT_ON(e.h2d[0].need(tot * sizeof(fe25519) + 32));
-    BP_EXIT_ON(e.h2d[1].need(tot * sizeof(fe25519) + 32));
-    BP_EXIT_ON(e.h2d[2].need(num_vectors * sizeof(fe25519)));
+    BP_EXIT_ON(e.op_a.need(tot * sizeof(fe25519) + 32));
+    BP_EXIT_ON(e.op_b.need(tot * sizeof(fe25519) + 32));
+    BP_EXIT_ON(e.op_out.need(num_vectors * sizeof(fe25519)));
     for (size_t i = 0; i < num_vectors; i++) {
-        BP_EXIT_ON(hipMemcpyAsync(e.h2d[0].as<fe25519>() + i * n, a_vectors[i].elements, n * sizeof(fe25519),
+        BP_EXIT_ON(hipMemcpyAsync(e.op_a.as<fe25519>() + i * n, a_vectors[i].elements, n * sizeof(fe25519),
                                   hipMemcpyHostToDevice, e.stream));
-        BP_EXIT_ON(hipMemcpyAsync(e.h2d[1].as<fe25519>() + i * n, b_vectors[i].elements, n * sizeof(fe25519),
+        BP_EXIT_ON(hipMemcpyAsync(e.op_b.as<fe25519>() + i * n, b_vectors[i].elements, n * sizeof(fe25519),
                                   hipMemcpyHostToDevice, e.stream));
     }
-    bp::launch_ip_batch(e.h2d[2].as<bp::fe>(), e.h2d[0].as<bp::fe>(), e.h2d[1].as<bp::fe>(), n, num_vectors, e.stream);
+    bp::launch_ip_batch(e.op_out.as<bp::fe>(), e.op_a.as<bp::fe>(), e.op_b.as<bp::fe>(), n, num_vectors, e.stream);
     BP_EXIT_ON(hipGetLastError());
-    BP_EXIT_ON(hipMemcpyAsync(results, e.h2d[2].p, num_vectors * sizeof(fe25519), hipMemcpyDeviceToHost, e.stream));
+    BP_EXIT_ON(hipMemcpyAsync(results, e.op_out.p, num_vectors * sizeof(fe25519), hipMemcpyDeviceToHost, e.stream));
     BP_EXIT_ON(hipStreamSynchronize(e.stream));
 }
 
@@ -1721,17 +1567,17 @@ static void field_common(int op, fe25519* results, const fe25519* a, const fe255
     if (count == 0) return;
     Engine& e = engine_or_exit();
     std::lock_guard<std::mutex> lk(e.mu);
-    BP_EXIT_ON(e.h2d[0].need(count * sizeof(fe25519)));
-    BP_EXIT_ON(e.h2d[1].need(count * sizeof(fe25519)));
-    BP_EXIT_ON(e.h2d[2].need(count * sizeof(fe25519)));
-    BP_EXIT_ON(hipMemcpyAsync(e.h2d[0].p, a, count * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
-    if (b) BP_EXIT_ON(hipMemcpyAsync(e.h2d[1].p, b, count * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
+    BP_EXIT_ON(e.op_a.need(count * sizeof(fe25519)));
+    BP_EXIT_ON(e.op_b.need(count * sizeof(fe25519)));
+    BP_EXIT_ON(e.op_out.need(count * sizeof(fe25519)));
+    BP_EXIT_ON(hipMemcpyAsync(e.op_a.p, a, count * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
+    if (b) BP_EXIT_ON(hipMemcpyAsync(e.op_b.p, b, count * sizeof(fe25519), hipMemcpyHostToDevice, e.stream));
     if (op == 5)
-        bp::launch_invert(e.h2d[2].as<bp::fe>(), e.h2d[0].as<bp::fe>(), count, e.stream);
+        bp::launch_invert(e.op_out.as<bp::fe>(), e.op_a.as<bp::fe>(), count, e.stream);
     else
-        bp::launch_field_op(op, e.h2d[2].as<bp::fe>(), e.h2d[0].as<bp::fe>(), e.h2d[1].as<bp::fe>(), count, e.stream);
+        bp::launch_field_op(op, e.op_out.as<bp::fe>(), e.op_a.as<bp::fe>(), e.op_b.as<bp::fe>(), count, e.stream);
     BP_EXIT_ON(hipGetLastError());
-    BP_EXIT_ON(hipMemcpyAsync(results, e.h2d[2].p, count * sizeof(fe25519), hipMemcpyDeviceToHost, e.stream));
+    BP_EXIT_ON(hipMemcpyAsync(results, e.op_out.p, count * sizeof(fe25519), hipMemcpyDeviceToHost, e.stream));
     BP_EXIT_ON(hipStreamSynchronize(e.stream));
 }
 
@@ -1750,46 +1596,14 @@ static bool stage_single(Engine& e, const InnerProductProof* ip, const RangeProo
                          hipbp_proof_batch* b) {
     size_t abl = ip->a.length, Lr = ip->L_len;
     if (ip->b.length != abl || abl == 0 || ip->L.length < Lr || ip->R.length < Lr) return false;
-    // head: V,A,S,T1,T2 | t,c,x ; then a,b ; then L,R
-    size_t bytes = 5 * sizeof(ge25519) + 3 * sizeof(fe25519) + 2 * abl * sizeof(fe25519) + 2 * Lr * sizeof(ge25519);
-    BP_EXIT_ON(e.h2d[3].need(bytes));
+    const bp::ChunkLayout lay{1, abl, Lr};
+    const size_t bytes = lay.bytes();
+    BP_EXIT_ON(e.proof1.need(bytes));
     BP_EXIT_ON(e.need_pinned(bytes));
     BP_EXIT_ON(hipStreamSynchronize(e.stream));   // previous user of the staging buffer is done
-    uint8_t* q = e.pinned;
-    auto put = [&](const void* src, size_t len) {
-        if (src) memcpy(q, src, len);
-        else memset(q, 0, len);
-        q += len;
-    };
-    const ge25519 zero_pt = {};
-    put(V ? V : &zero_pt, sizeof(ge25519));
-    put(rp ? &rp->A : nullptr, sizeof(ge25519));
-    put(rp ? &rp->S : nullptr, sizeof(ge25519));
-    put(rp ? &rp->T1 : nullptr, sizeof(ge25519));
-    put(rp ? &rp->T2 : nullptr, sizeof(ge25519));
-    put(rp ? &rp->t : nullptr, sizeof(fe25519));
-    put(&ip->c, sizeof(fe25519));
-    put(&ip->x, sizeof(fe25519));
-    put(ip->a.elements, abl * sizeof(fe25519));
-    put(ip->b.elements, abl * sizeof(fe25519));
-    if (Lr) {
-        put(ip->L.elements, Lr * sizeof(ge25519));
-        put(ip->R.elements, Lr * sizeof(ge25519));
-    }
-    BP_EXIT_ON(hipMemcpyAsync(e.h2d[3].p, e.pinned, bytes, hipMemcpyHostToDevice, e.stream));
-    uint8_t* d = e.h2d[3].as<uint8_t>();
-    const ge25519* pts = (const ge25519*)d;
-    const fe25519* fes = (const fe25519*)(d + 5 * sizeof(ge25519));
-    b->count = 1;
-    b->ab_len = abl;
-    b->L_len = Lr;
-    b->V = pts + 0; b->A = pts + 1; b->S = pts + 2; b->T1 = pts + 3; b->T2 = pts + 4;
-    b->t = fes + 0; b->c = fes + 1; b->x = fes + 2;
-    b->a = fes + 3;
-    b->b = fes + 3 + abl;
-    const ge25519* lr = (const ge25519*)(d + 5 * sizeof(ge25519) + (3 + 2 * abl) * sizeof(fe25519));
-    b->L = Lr ? lr : nullptr;
-    b->R = Lr ? lr + Lr : nullptr;
+    lay.pack(e.pinned.p, 0, *ip, rp, V);
+    BP_EXIT_ON(hipMemcpyAsync(e.proof1.p, e.pinned.p, bytes, hipMemcpyHostToDevice, e.stream));
+    lay.view(e.proof1.p, b);
     return true;
 }
 
@@ -1802,10 +1616,10 @@ static bool verify_single(const InnerProductProof* ip, const RangeProof* rp, con
     if (!stage_single(e, ip, rp, V, &b)) return false;
     b.n = n;
     // generators + h + P
-    const size_t cap0 = e.h2d[4].cap;
-    BP_EXIT_ON(e.h2d[4].need(2 * n * sizeof(ge25519) + 3 * sizeof(ge25519)));
-    if (e.h2d[4].cap != cap0) e.single_gens.clear();   // a new buffer (maybe at the old address) holds nothing
-    ge25519* dg = e.h2d[4].as<ge25519>();
+    const size_t cap0 = e.gens1.cap;
+    BP_EXIT_ON(e.gens1.need(2 * n * sizeof(ge25519) + 3 * sizeof(ge25519)));
+    if (e.gens1.cap != cap0) e.single_gens.clear();   // a new buffer (maybe at the old address) holds nothing
+    ge25519* dg = e.gens1.as<ge25519>();
     const size_t GB = n * sizeof(ge25519);
     std::vector<uint8_t>& sg = e.single_gens;
     const bool same = e.single_gens_dev == (const void*)dg && sg.size() == 2 * GB + sizeof(ge25519) &&
@@ -1822,8 +1636,8 @@ static bool verify_single(const InnerProductProof* ip, const RangeProof* rp, con
         e.single_gens_dev = dg;
     }
     if (P) BP_EXIT_ON(hipMemcpyAsync(dg + 2 * n + 1, P, sizeof(ge25519), hipMemcpyHostToDevice, e.stream));
-    BP_EXIT_ON(e.h2d[5].need(64));
-    int rc = run_verify(e, &b, P ? dg + 2 * n + 1 : nullptr, dg, dg + n, dg + 2 * n, e.h2d[5].as<uint8_t>(), nullptr,
+    BP_EXIT_ON(e.ok1.need(64));
+    int rc = run_verify(e, &b, P ? dg + 2 * n + 1 : nullptr, dg, dg + n, dg + 2 * n, e.ok1.as<uint8_t>(), nullptr,
                         nullptr, rp != nullptr ? 1 : 0, e.stream);
     if (rc == HIPBP_ERR_ARG) {
         fprintf(stderr, "Error: %s\n", g_err.c_str());
@@ -1834,7 +1648,7 @@ static bool verify_single(const InnerProductProof* ip, const RangeProof* rp, con
         exit(EXIT_FAILURE);
     }
     uint8_t ok = 0;
-    BP_EXIT_ON(hipMemcpyAsync(&ok, e.h2d[5].p, 1, hipMemcpyDeviceToHost, e.stream));
+    BP_EXIT_ON(hipMemcpyAsync(&ok, e.ok1.p, 1, hipMemcpyDeviceToHost, e.stream));
     BP_EXIT_ON(hipStreamSynchronize(e.stream));
     return ok != 0;
 }
@@ -1871,36 +1685,24 @@ namespace {
 int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t* idx, size_t B, size_t abl,
                size_t Lr, size_t n, const PointVector* G, const PointVector* H, const ge25519* h, uint8_t* ok) {
     BP_RET_ON(hipSetDevice(dev));
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    BP_RET_ON(err);
+    BP_ENGINE_OR_RET(e);
     constexpr size_t CHUNK = 1024;
-    const size_t GE = sizeof(ge25519), FE = sizeof(fe25519);
-    // per chunk of c proofs: V A S T1 T2 [c] | t c x [c] | a b [c abl] | L R [c Lr]
-    auto chunk_bytes = [&](size_t c) { return c * (5 * GE + 3 * FE + 2 * abl * FE + 2 * Lr * GE); };
+    const size_t GE = bp::GE;
+    auto chunk_bytes = [&](size_t c) { return bp::ChunkLayout{c, abl, Lr}.bytes(); };
     const size_t nch = (B + CHUNK - 1) / CHUNK;
     const size_t gen_off = chunk_bytes(CHUNK) * (nch - 1) + chunk_bytes(B - CHUNK * (nch - 1));
     const size_t ok_off = gen_off + (2 * n + 1) * GE, bytes = ok_off + B;
     std::lock_guard<std::mutex> lk(e->mu);
     if (!e->stream2) BP_RET_ON(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
     hipStream_t st[2] = {e->stream, e->stream2};
-    if (bytes > e->host_pinned_cap) {
-        if (e->host_pinned) {
-            BP_RET_ON(hipStreamSynchronize(st[0]));
-            BP_RET_ON(hipStreamSynchronize(st[1]));
-            BP_RET_ON(hipHostFree(e->host_pinned));
-            e->host_pinned = nullptr;
-            e->host_pinned_cap = 0;
-        }
-        BP_RET_ON(hipHostMalloc((void**)&e->host_pinned, bytes));
-        e->host_pinned_cap = bytes;
-    }
-    if (bytes > e->host_dev.cap) {   // Buf::need frees the old buffer: nothing may still read it
+    // need() frees a buffer that grows: nothing may still read either
+    if ((bytes > e->host_pinned.cap && e->host_pinned.p) || bytes > e->host_dev.cap) {
         BP_RET_ON(hipStreamSynchronize(st[0]));
         BP_RET_ON(hipStreamSynchronize(st[1]));
     }
+    BP_RET_ON(e->host_pinned.need(bytes));
     BP_RET_ON(e->host_dev.need(bytes));
-    uint8_t* host = e->host_pinned;
+    uint8_t* host = e->host_pinned.as<uint8_t>();
     uint8_t* dbuf = e->host_dev.as<uint8_t>();
     memcpy(host + gen_off, G->elements, n * GE);
     memcpy(host + gen_off + n * GE, H->elements, n * GE);
@@ -1943,10 +1745,7 @@ int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t
     for (int k = 0; k < 2 && rc == HIPBP_OK; k++) {
         rc = pipeline_for(*e, st[k], std::min(B, CHUNK), (int)n, 1, &pl[k]);
         if (rc == HIPBP_OK) {
-            pl[k]->G = (const bp::ge*)dgen;
-            pl[k]->H = (const bp::ge*)(dgen + n);
-            pl[k]->h = (const bp::ge*)(dgen + 2 * n);
-            pl[k]->g = nullptr;
+            pl[k]->set_gens(dgen, dgen + n, nullptr, dgen + 2 * n);
             // (the engine's one-shot pipelines are shared with the other entry points: the tables
             // are lent for this call only and taken back after the flush below)
             pl[k]->ext_tab = hb > 0 ? e->host_tab.as<bp::ge>() : nullptr;
@@ -1962,29 +1761,13 @@ int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t
     uint8_t* dok = dbuf + ok_off;
     size_t off = 0;
     for (size_t ch = 0; ch < nch && rc == HIPBP_OK; ch++) {
-        const size_t c0 = ch * CHUNK, c = std::min(CHUNK, B - c0), cb = chunk_bytes(c);
+        const size_t c0 = ch * CHUNK, c = std::min(CHUNK, B - c0);
+        const bp::ChunkLayout lay{c, abl, Lr};
+        const size_t cb = lay.bytes();
         uint8_t* hc = host + off;
-        ge25519* hg = (ge25519*)hc;
-        fe25519* hf = (fe25519*)(hc + 5 * c * GE);
-        fe25519* hab = hf + 3 * c;
-        ge25519* hlr = (ge25519*)(hab + 2 * c * abl);
         for (size_t k = 0; k < c; k++) {
             const RangeProof& p = proofs[idx[c0 + k]];
-            const InnerProductProof& ip = p.ip_proof;
-            hg[k] = V[idx[c0 + k]];
-            hg[c + k] = p.A;
-            hg[2 * c + k] = p.S;
-            hg[3 * c + k] = p.T1;
-            hg[4 * c + k] = p.T2;
-            hf[k] = p.t;
-            hf[c + k] = ip.c;
-            hf[2 * c + k] = ip.x;
-            memcpy(hab + k * abl, ip.a.elements, abl * FE);
-            memcpy(hab + (c + k) * abl, ip.b.elements, abl * FE);
-            if (Lr) {
-                memcpy(hlr + k * Lr, ip.L.elements, Lr * GE);
-                memcpy(hlr + (c + k) * Lr, ip.R.elements, Lr * GE);
-            }
+            lay.pack(hc, k, p.ip_proof, &p, &V[idx[c0 + k]]);
         }
         hipStream_t s = st[ch & 1];
         if ((err = hipMemcpyAsync(dbuf + off, hc, cb, hipMemcpyHostToDevice, s)) != hipSuccess) {
@@ -1992,21 +1775,10 @@ int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t
             rc = HIPBP_ERR_DEVICE;
             break;
         }
-        const uint8_t* dc = dbuf + off;
-        const ge25519* dg = (const ge25519*)dc;
-        const fe25519* df = (const fe25519*)(dc + 5 * c * GE);
         hipbp_proof_batch b;
         memset(&b, 0, sizeof b);
-        b.count = c;
         b.n = n;
-        b.ab_len = abl;
-        b.L_len = Lr;
-        b.V = dg; b.A = dg + c; b.S = dg + 2 * c; b.T1 = dg + 3 * c; b.T2 = dg + 4 * c;
-        b.t = df; b.c = df + c; b.x = df + 2 * c;
-        b.a = df + 3 * c; b.b = df + 3 * c + c * abl;
-        const ge25519* dlr = (const ge25519*)(df + 3 * c + 2 * c * abl);
-        b.L = Lr ? dlr : nullptr;
-        b.R = Lr ? dlr + c * Lr : nullptr;
+        lay.view(dbuf + off, &b);
         rc = pl[ch & 1]->push(&b, nullptr, dok + c0, nullptr, nullptr);
         off += cb;
     }
@@ -2235,10 +2007,9 @@ void cuda_benchmark_range_proof(int iterations, size_t bit_size) {
         for (int i = 0; i < 4; i++) scalar(r4[p * 4 + i]);
     }
     Engine& e = engine_or_exit();
-    const size_t Lc = Lr ? Lr : 1;
-    // device: inputs | generators | outputs (V A S T1 T2 [count], taux mu t c x a b [count], L R [count Lr], valid)
-    const size_t in_b = (count * (2 + 2 * n + 4)) * FE, gen_b = ng * GE;
-    const size_t out_b = count * (5 * GE + 7 * FE + 2 * Lc * GE) + count;
+    // device: inputs | generators | outputs (bp::OutLayout)
+    const bp::OutLayout lay{count, count, Lr, 0};
+    const size_t in_b = (count * (2 + 2 * n + 4)) * FE, gen_b = ng * GE, out_b = lay.end();
     uint8_t* d = nullptr;
     BP_EXIT_ON(hipMalloc(&d, in_b + gen_b + out_b));
     fe25519* dv = (fe25519*)d;
@@ -2255,14 +2026,7 @@ void cuda_benchmark_range_proof(int iterations, size_t bit_size) {
     BP_EXIT_ON(hipMemcpy(dr4, r4.data(), count * 4 * FE, hipMemcpyHostToDevice));
     BP_EXIT_ON(hipMemcpy(dgen, gen.data(), gen_b, hipMemcpyHostToDevice));
     hipbp_proof_out po;
-    ge25519* og = (ge25519*)o;
-    po.V = og; po.A = og + count; po.S = og + 2 * count; po.T1 = og + 3 * count; po.T2 = og + 4 * count;
-    fe25519* of = (fe25519*)(og + 5 * count);
-    po.taux = of; po.mu = of + count; po.t = of + 2 * count; po.c = of + 3 * count; po.x = of + 4 * count;
-    po.a = of + 5 * count; po.b = of + 6 * count;
-    ge25519* olr = (ge25519*)(of + 7 * count);
-    po.L = olr; po.R = olr + count * Lc;
-    po.valid = (uint8_t*)(olr + 2 * count * Lc);
+    lay.view(o, &po);
     hipbp_prove_input pin{count, n, dv, dgam, dsL, dsR, dr4};
     if (hipbp_batch_generate_range_proof(&pin, dgen, dgen + n, dgen + 2 * n, dgen + 2 * n + 1, &po, nullptr) !=
         HIPBP_OK) {
@@ -2273,28 +2037,14 @@ void cuda_benchmark_range_proof(int iterations, size_t bit_size) {
     std::vector<uint8_t> host(out_b);
     BP_EXIT_ON(hipMemcpy(host.data(), o, out_b, hipMemcpyDeviceToHost));
     BP_EXIT_ON(hipFree(d));
-    const ge25519* hg = (const ge25519*)host.data();
-    const fe25519* hf = (const fe25519*)(hg + 5 * count);
-    const ge25519* hlr = (const ge25519*)(hf + 7 * count);
-    std::vector<fe25519> ha(hf + 5 * count, hf + 6 * count), hb(hf + 6 * count, hf + 7 * count);
-    std::vector<ge25519> hL(hlr, hlr + count * Lc), hR(hlr + count * Lc, hlr + 2 * count * Lc);
     std::vector<RangeProof> proofs(count);
-    std::vector<ge25519> V(hg, hg + count);
+    std::vector<ge25519> V(count);
     for (size_t p = 0; p < count; p++) {
-        RangeProof& rp = proofs[p];
-        memset(&rp, 0, sizeof rp);
-        rp.V = hg[p]; rp.A = hg[count + p]; rp.S = hg[2 * count + p]; rp.T1 = hg[3 * count + p];
-        rp.T2 = hg[4 * count + p];
-        rp.taux = hf[p]; rp.mu = hf[count + p]; rp.t = hf[2 * count + p];
-        InnerProductProof& ip = rp.ip_proof;
-        ip.n = n;
-        ip.a.elements = &ha[p]; ip.a.length = 1;
-        ip.b.elements = &hb[p]; ip.b.length = 1;
-        ip.c = hf[3 * count + p];
-        ip.x = hf[4 * count + p];
-        ip.L.elements = Lr ? &hL[p * Lr] : nullptr; ip.L.length = Lr;
-        ip.R.elements = Lr ? &hR[p * Lr] : nullptr; ip.R.length = Lr;
-        ip.L_len = Lr;
+        if (lay.unpack(host.data(), p, n, proofs[p]) < 0) {
+            fprintf(stderr, "Error: Failed to allocate memory for field vector\n");
+            exit(1);
+        }
+        V[p] = proofs[p].V;
     }
     PointVector Gv = {gen.data(), n}, Hv = {gen.data() + n, n};
     const ge25519 *g = &gen[2 * n], *h = &gen[2 * n + 1];
@@ -2316,6 +2066,8 @@ void cuda_benchmark_range_proof(int iterations, size_t bit_size) {
     for (size_t p = 0; p < count; p++) {
         pass += ok1[p];
         agree += ok1[p] == ok2[p];
+        InnerProductProof& ip = proofs[p].ip_proof;
+        free(ip.a.elements); free(ip.b.elements); free(ip.L.elements); free(ip.R.elements);
     }
     printf("cuda_benchmark_range_proof: n=%zu  %zu proofs  cuda_range_proof_verify %.3f ms/call  "
            "batched (hipbp_batch_range_proof_verify_host) %.1f verifies/s  passes %zu/%zu  verdicts agree %zu/%zu\n",

@@ -1,0 +1,246 @@
+// bp_layout.h — the flat batch layouts and the engine's workspace tables (internal to the library).
+// Host-only and pure: no HIP runtime calls, so tests/layout_check.hip checks every offset, the
+// pack / view / unpack round trips and every buffer size on a CPU.
+#pragma once
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/cudabulletproof_hip.h"
+#include "bp_kernels.h"
+
+namespace bp {
+
+constexpr size_t FE = 32, GE = 128;   // sizeof(fe25519), sizeof(ge25519)
+static_assert(sizeof(fe25519) == FE && sizeof(ge25519) == GE, "wire record sizes");
+
+// ------------------------------------------------------------------ verify chunk
+// c proofs of one (ab_len, L_len) shape in the flat wire format, no padding:
+//   V A S T1 T2 [c] | t c x [c] | a b [c abl] | L R [c Lr]
+// The same bytes in pinned host memory (pack) and in device memory (view).
+struct ChunkLayout {
+    size_t c, abl, Lr;
+    size_t o_fe() const { return 5 * c * GE; }
+    size_t o_ab() const { return o_fe() + 3 * c * FE; }
+    size_t o_lr() const { return o_ab() + 2 * c * abl * FE; }
+    size_t bytes() const { return o_lr() + 2 * c * Lr * GE; }
+    // count, ab_len, L_len and the twelve pointers of `b` over the chunk at `base` (n, taux, mu, Vp
+    // are the caller's)
+    void view(const void* base, hipbp_proof_batch* b) const {
+        const uint8_t* q = (const uint8_t*)base;
+        const ge25519* pt = (const ge25519*)q;
+        const fe25519* f = (const fe25519*)(q + o_fe());
+        const fe25519* ab = (const fe25519*)(q + o_ab());
+        const ge25519* lr = (const ge25519*)(q + o_lr());
+        b->count = c; b->ab_len = abl; b->L_len = Lr;
+        b->V = pt; b->A = pt + c; b->S = pt + 2 * c; b->T1 = pt + 3 * c; b->T2 = pt + 4 * c;
+        b->t = f; b->c = f + c; b->x = f + 2 * c;
+        b->a = ab; b->b = ab + c * abl;
+        b->L = Lr ? lr : nullptr;
+        b->R = Lr ? lr + c * Lr : nullptr;
+    }
+    // proof k of the chunk at `base` (host memory) from ip (a, b of abl elements, L, R of at least
+    // Lr), the range proof's A S T1 T2 t and V; a missing rp or V is written as zeros
+    void pack(void* base, size_t k, const InnerProductProof& ip, const RangeProof* rp, const ge25519* V) const {
+        uint8_t* q = (uint8_t*)base;
+        ge25519* pt = (ge25519*)q;
+        fe25519* f = (fe25519*)(q + o_fe());
+        fe25519* ab = (fe25519*)(q + o_ab());
+        ge25519* lr = (ge25519*)(q + o_lr());
+        const ge25519 zp = {};
+        const fe25519 zf = {};
+        pt[k] = V ? *V : zp;
+        pt[c + k] = rp ? rp->A : zp;
+        pt[2 * c + k] = rp ? rp->S : zp;
+        pt[3 * c + k] = rp ? rp->T1 : zp;
+        pt[4 * c + k] = rp ? rp->T2 : zp;
+        f[k] = rp ? rp->t : zf;
+        f[c + k] = ip.c;
+        f[2 * c + k] = ip.x;
+        auto put = [](void* dst, const void* src, size_t len) {   // (a null vector: zeros, too)
+            if (src) memcpy(dst, src, len);
+            else memset(dst, 0, len);
+        };
+        put(ab + k * abl, ip.a.elements, abl * FE);
+        put(ab + (c + k) * abl, ip.b.elements, abl * FE);
+        if (Lr) {
+            put(lr + k * Lr, ip.L.elements, Lr * GE);
+            put(lr + (c + k) * Lr, ip.R.elements, Lr * GE);
+        }
+    }
+};
+
+// ------------------------------------------------------------------ proof vectors
+// A proof's a, b (length 1) and L, R (Lr points; 1 byte when Lr = 0) malloc'ed as the reference's
+// inner_product_proof_init / field_vector_copy leave them, and n and the lengths set.  False: an
+// allocation failed (what was allocated is in the proof, for the caller to free).
+inline bool proof_vectors_alloc(InnerProductProof& ip, size_t n, size_t Lr) {
+    ip.a.elements = (fe25519*)malloc(FE);
+    ip.b.elements = (fe25519*)malloc(FE);
+    ip.L.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
+    ip.R.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
+    ip.n = n;
+    ip.a.length = ip.b.length = 1;
+    ip.L.length = ip.R.length = ip.L_len = Lr;
+    return ip.a.elements && ip.b.elements && ip.L.elements && ip.R.elements;
+}
+
+// ------------------------------------------------------------------ proof output
+// The prover's outputs, after `lead` bytes of the owner's own (the prove-host slot's v | gamma):
+//   V A S T1 T2 | taux mu t c x a b | L R | valid
+// Every region is sized for cap proofs; the arrays of the c <= cap proofs present sit packed at
+// stride c at the front of each (a short last chunk).
+struct OutLayout {
+    size_t cap, c, Lr, lead;
+    size_t o_pts() const { return lead; }
+    size_t o_fe() const { return o_pts() + 5 * cap * GE; }
+    size_t o_lr() const { return o_fe() + 7 * cap * FE; }
+    size_t o_valid() const { return o_lr() + 2 * cap * Lr * GE; }
+    size_t end() const { return o_valid() + cap; }
+    size_t slot_bytes() const { return (end() + 127) & ~(size_t)127; }
+    size_t used() const { return o_valid() + c - o_pts(); }   // points .. valid[c): one D2H copy
+    void view(void* base, hipbp_proof_out* o) const {
+        uint8_t* q = (uint8_t*)base;
+        ge25519* pt = (ge25519*)(q + o_pts());
+        fe25519* f = (fe25519*)(q + o_fe());
+        ge25519* lr = (ge25519*)(q + o_lr());
+        o->V = pt; o->A = pt + c; o->S = pt + 2 * c; o->T1 = pt + 3 * c; o->T2 = pt + 4 * c;
+        o->taux = f; o->mu = f + c; o->t = f + 2 * c; o->c = f + 3 * c; o->x = f + 4 * c;
+        o->a = f + 5 * c; o->b = f + 6 * c;
+        o->L = Lr ? lr : nullptr;
+        o->R = Lr ? lr + c * Lr : nullptr;
+        o->valid = q + o_valid();
+    }
+    // Proof k of a host copy into p (n = 1 << Lr): 1 a valid proof, its vectors malloc'ed; 0 a refused
+    // one (the five points and taux, mu, t; ip_proof all zero); -1 an allocation failed (p owns what
+    // was allocated)
+    int unpack(const void* base, size_t k, size_t n, RangeProof& p) const {
+        hipbp_proof_out o;
+        view(const_cast<void*>(base), &o);   // (read only)
+        p.V = o.V[k]; p.A = o.A[k]; p.S = o.S[k]; p.T1 = o.T1[k]; p.T2 = o.T2[k];
+        p.taux = o.taux[k]; p.mu = o.mu[k]; p.t = o.t[k];
+        InnerProductProof& ip = p.ip_proof;
+        memset(&ip, 0, sizeof ip);
+        if (!o.valid[k]) return 0;
+        if (!proof_vectors_alloc(ip, n, Lr)) return -1;
+        ip.c = o.c[k]; ip.x = o.x[k];
+        *ip.a.elements = o.a[k]; *ip.b.elements = o.b[k];
+        if (Lr) {
+            memcpy(ip.L.elements, o.L + k * Lr, Lr * GE);
+            memcpy(ip.R.elements, o.R + k * Lr, Lr * GE);
+        }
+        return 1;
+    }
+};
+
+// ------------------------------------------------------------------ workspace tables
+// One line per device buffer: X(id, field, type, bytes) — the engine's buffer `id` backs `field`, a
+// type*, of the workspace struct the kernels take, and holds `bytes` bytes.  The engine keeps one
+// grow-only allocation per id (0 bytes: not needed by this call, left as it is) and fills the
+// struct from the same table, BP_BUF_FIELD with the struct as `w` and the buffers as `b`.
+#define BP_BUF_ID(id, field, type, bytes) id,
+#define BP_BUF_SIZE(id, field, type, bytes) sz[id] = (bytes);
+#define BP_BUF_FIELD(id, field, type, bytes) w.field = (type*)b[id].p;
+constexpr size_t U32 = sizeof(uint32_t);
+
+// The prover (ProveWs) for B proofs of n bits; cap = B (4n + 4), its term items.  slist, sbins: with
+// terms0's heavy-list sort only.
+#define BP_PROVE_BUFS(X)                               \
+    X(PB_PS, ps, fe, B * 4 * n * FE)                   \
+    X(PB_PTERM, pterm, ge, cap * GE)                   \
+    X(PB_CHAIN, chain, ge, B * 4 * GE)                 \
+    X(PB_PTS, pts, ge, B * 5 * GE)                     \
+    X(PB_ST, st, fe, B * 8 * FE)                       \
+    X(PB_TSC, tsc, fe, B * 4 * FE)                     \
+    X(PB_TT, tt, ge, B * 4 * GE)                       \
+    X(PB_ACUR, acur, fe, B * n * FE)                   \
+    X(PB_BCUR, bcur, fe, B * n * FE)                   \
+    X(PB_ISCAL, iscal, fe, B * 2 * n * FE)             \
+    X(PB_CSC, csc, fe, B * 2 * FE)                     \
+    X(PB_ITERM, iterm, ge, B * (2 * n + 2) * GE)       \
+    X(PB_MISC, misc, fe, B * 4 * FE)                   \
+    X(PB_VALID, valid, uint8_t, B)                     \
+    X(PB_LIST, list, uint32_t, 2 * cap * U32)          \
+    X(PB_CNT, cnt, unsigned, 2 * U32)                  \
+    X(PB_CTAB, ctab, ge, 2 * n * GE)                   \
+    X(PB_SLIST, slist, uint32_t, sort ? cap * U32 : 0) \
+    X(PB_SBINS, sbins, unsigned, sort ? MSM_BINS * U32 : 0)
+enum ProveBuf { BP_PROVE_BUFS(BP_BUF_ID) PB_COUNT };
+inline size_t prove_cap(size_t B, size_t n) { return B * (4 * n + 4); }
+inline void prove_sizes(size_t B, size_t n, bool sort, size_t (&sz)[PB_COUNT]) {
+    const size_t cap = prove_cap(B, n);
+    BP_PROVE_BUFS(BP_BUF_SIZE)
+}
+
+// One chunk of the stand-alone IPA prover (IpaWs): Bc proofs of n elements, cap = 2n + 2 items each.
+#define BP_IPA_BUFS(X)                            \
+    X(IB_A, a, fe, Bc * n * FE)                   \
+    X(IB_B, b, fe, Bc * n * FE)                   \
+    X(IB_PROD, prod, fe, Bc * n * FE)             \
+    X(IB_SC, sc, fe, Bc * 2 * n * FE)             \
+    X(IB_CSC, csc, fe, Bc * 2 * FE)               \
+    X(IB_TERM, term, ge, Bc * 2 * n * GE)         \
+    X(IB_CQ, cq, ge, Bc * 2 * GE)                 \
+    X(IB_CHAIN, chain, ge, Bc * 4 * GE)           \
+    X(IB_TR, tr, fe, Bc * FE)                     \
+    X(IB_UU, uu, fe, Bc * 2 * FE)                 \
+    X(IB_X, x, fe, Bc * FE)                       \
+    X(IB_SLIST, slist, uint32_t, Bc * cap * U32)  \
+    X(IB_LLIST, llist, uint32_t, Bc * cap * U32)  \
+    X(IB_CTL, ctl, unsigned, (MSM_BINS + 2) * U32)
+enum IpaBuf { BP_IPA_BUFS(BP_BUF_ID) IB_COUNT };
+inline size_t ipa_cap(size_t n) { return 2 * n + 2; }
+// the bytes one more proof adds to a chunk (everything but ctl): the chunking rule's unit
+inline size_t ipa_per_proof(size_t n) { return (5 * n + 6) * FE + (2 * n + 6) * GE + 2 * ipa_cap(n) * U32; }
+inline void ipa_sizes(size_t Bc, size_t n, size_t (&sz)[IB_COUNT]) {
+    const size_t cap = ipa_cap(n);
+    BP_IPA_BUFS(BP_BUF_SIZE)
+}
+
+// A verify slot (VerifyWs) for B proofs of n bits with Lb fold rounds; Lc = max(Lb, 1); m2 = B in mode 2
+// (range_proof_verify), whose buffers the other modes leave unallocated.  B_PERM, the lane orders,
+// is no VerifyWs field: the batch's sort sets size it.
+#define BP_VERIFY_BUFS(X)                         \
+    X(B_SG, sG, fe, B * FE)                       \
+    X(B_SH, sH, fe, B * n * FE)                   \
+    X(B_SC, sc, fe, B * 4 * FE)                   \
+    X(B_U, u, fe, B * Lc * FE)                    \
+    X(B_UINV, uinv, fe, B * Lc * FE)              \
+    X(B_IPOK, ipok, uint8_t, B)                   \
+    X(B_MSM_PTS, msm_pts, ge, B * 2 * n * GE)     \
+    X(B_MSM_PART, msm_part, ge, B * 2 * GE)       \
+    X(B_TERMS, terms, ge, B * 4 * GE)             \
+    X(B_FOLD0, fold[0], ge, B * 2 * n * GE)       \
+    X(B_FOLD1, fold[1], ge, B * 2 * n * GE)       \
+    X(B_FIN, fin, ge, B * 2 * GE)                 \
+    X(B_PIN, Pin, ge, B * GE)                     \
+    X(B_PSC, psc, fe, m2 * 8 * FE)                \
+    X(B_PTERM, pterm, ge, m2 * 8 * GE)            \
+    X(B_LR, lr, ge, m2 * 2 * GE)                  \
+    X(B_CHAL, chal, fe, m2 * FE)                  \
+    X(B_M3, m3, ge, m2 * 2 * GE)                  \
+    X(B_RFLAGS, rflags, uint8_t, m2)              \
+    X(B_PBASE, pbase, ge, m2 * 3 * GE)
+enum VerifyBuf { BP_VERIFY_BUFS(BP_BUF_ID) B_PERM, B_COUNT };
+inline void verify_sizes(size_t B, size_t n, size_t Lb, int range_mode, size_t (&sz)[B_COUNT]) {
+    const size_t Lc = Lb ? Lb : 1, m2 = range_mode == 2 ? B : 0;
+    BP_VERIFY_BUFS(BP_BUF_SIZE)
+    sz[B_PERM] = 0;
+}
+
+// The canonical-tree MSM (launch_msm_full: `count` MSMs of n points) and the point tree
+// (launch_tree_full of n points) share one per-stream set; each call sizes its own buffers.
+enum MsmBuf { MB_TERMS, MB_ROOT0, MB_ROOT1, MB_TREE0, MB_TREE1, MB_ORDER, MB_BINS, MB_COUNT };
+inline void msm_sizes(size_t n, size_t count, size_t (&sz)[MB_COUNT]) {
+    const size_t tot = n * count, nb = count * ((n + 255) / 256);
+    sz[MB_TERMS] = tot * GE;                 // per-point terms
+    sz[MB_ROOT0] = sz[MB_ROOT1] = nb * GE;   // block roots
+    sz[MB_TREE0] = sz[MB_TREE1] = 0;
+    sz[MB_ORDER] = tot * U32;                // lane order
+    sz[MB_BINS] = MSM_BINS * U32;            // its sort bins
+}
+inline void tree_sizes(size_t n, size_t (&sz)[MB_COUNT]) {
+    for (size_t& s : sz) s = 0;
+    sz[MB_TREE0] = sz[MB_TREE1] = (n + 255) / 256 * GE;   // tree ping-pong
+}
+
+}  // namespace bp

@@ -1,0 +1,325 @@
+// layout_check.hip — TEST INFRASTRUCTURE (tests/test_layout.py).
+//
+// Runs the flat batch layouts and workspace tables of cudabulletproof_amd/csrc/bp_layout.h (host-only)
+// on the CPU.  The expected offsets and sizes are restated here as plain formulas (32-byte field
+// elements, 128-byte points), independent of the header's own constants and helpers.
+//   offsets:   the verify chunk and the proof output over a sweep of shapes: every region where the
+//              formulas put it, in order, disjoint, 32-byte aligned relative to the base
+//   pack:      proofs with distinct bytes in every field, packed and read back through the batch view
+//   unpack:    a pattern written through the hipbp_proof_out view, unpacked into RangeProof structs
+//   tables:    every workspace buffer's bytes
+// Prints "<checks> <failures>"; exit status 1 on any failure.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../cudabulletproof_amd/csrc/bp_layout.h"
+
+typedef unsigned long long u64;
+static u64 checks = 0, fails = 0;
+#define CHECK(cond, ...)                                    \
+    do {                                                    \
+        checks++;                                           \
+        if (!(cond)) {                                      \
+            if (fails++ < 20) {                             \
+                std::printf("FAIL line %d: ", __LINE__);    \
+                std::printf(__VA_ARGS__);                   \
+                std::printf("\n");                          \
+            }                                               \
+        }                                                   \
+    } while (0)
+
+// deterministic distinct bytes
+static u64 g_state = 0x1234567;
+static void fill(void* p, size_t len) {
+    uint8_t* q = (uint8_t*)p;
+    for (size_t i = 0; i < len; i++) {
+        g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
+        q[i] = (uint8_t)(g_state >> 56) | 1;   // never zero: a zeroed region is told apart
+    }
+}
+template <class T>
+static bool same(const T& a, const T& b) { return memcmp(&a, &b, sizeof(T)) == 0; }
+static bool all_zero(const void* p, size_t len) {
+    for (size_t i = 0; i < len; i++) if (((const uint8_t*)p)[i]) return false;
+    return true;
+}
+
+struct Region { const void* p; size_t len; };
+// the regions start at base + off0, follow each other in order without overlap, each 32-byte aligned
+// relative to the base; returns the end offset of the last
+static size_t check_regions(const uint8_t* base, const std::vector<Region>& rg, const std::vector<size_t>& want) {
+    size_t end = 0;
+    for (size_t i = 0; i < rg.size(); i++) {
+        const size_t off = (size_t)((const uint8_t*)rg[i].p - base);
+        CHECK(off == want[i], "region %zu at %zu, want %zu", i, off, want[i]);
+        CHECK(off % 32 == 0, "region %zu not 32-byte aligned", i);
+        CHECK(off >= end, "region %zu overlaps its predecessor", i);
+        end = off + rg[i].len;
+    }
+    return end;
+}
+
+static void offsets() {
+    const size_t cs[] = {1, 2, 3, 1024}, abls[] = {1, 2, 3}, Lrs[] = {0, 1, 6, 16};
+    for (size_t c : cs)
+        for (size_t Lr : Lrs) {
+            for (size_t abl : abls) {
+                const bp::ChunkLayout l{c, abl, Lr};
+                const size_t bytes = c * (5 * 128 + 3 * 32 + 2 * abl * 32 + 2 * Lr * 128);
+                CHECK(l.bytes() == bytes, "chunk bytes c=%zu abl=%zu Lr=%zu", c, abl, Lr);
+                uint8_t* base = (uint8_t*)malloc(bytes);
+                hipbp_proof_batch b;
+                memset(&b, 0xEE, sizeof b);
+                l.view(base, &b);
+                CHECK(b.count == c && b.ab_len == abl && b.L_len == Lr, "chunk view header");
+                std::vector<Region> rg = {{b.V, c * 128}, {b.A, c * 128}, {b.S, c * 128}, {b.T1, c * 128}, {b.T2, c * 128},
+                                          {b.t, c * 32}, {b.c, c * 32}, {b.x, c * 32}, {b.a, c * abl * 32},
+                                          {b.b, c * abl * 32}};
+                std::vector<size_t> want;
+                for (size_t i = 0; i < 5; i++) want.push_back(i * c * 128);
+                for (size_t i = 0; i < 3; i++) want.push_back(5 * c * 128 + i * c * 32);
+                for (size_t i = 0; i < 2; i++) want.push_back(5 * c * 128 + 3 * c * 32 + i * c * abl * 32);
+                if (Lr) {
+                    rg.push_back({b.L, c * Lr * 128});
+                    rg.push_back({b.R, c * Lr * 128});
+                    for (size_t i = 0; i < 2; i++)
+                        want.push_back(5 * c * 128 + 3 * c * 32 + 2 * c * abl * 32 + i * c * Lr * 128);
+                } else {
+                    CHECK(!b.L && !b.R, "L, R must be null at Lr = 0");
+                }
+                CHECK(check_regions(base, rg, want) == bytes, "chunk regions do not fill the chunk");
+                free(base);
+            }
+            const size_t caps[] = {c, c + 1, 16384};
+            for (size_t CH : caps)
+                for (int with_lead = 0; with_lead < 2; with_lead++) {
+                    // the prove-host slot's formulas (lead = its v | gamma region; 0: outputs alone)
+                    const size_t o_pts = with_lead ? 2 * CH * 32 : 0, o_fe = o_pts + 5 * CH * 128;
+                    const size_t o_lr = o_fe + 7 * CH * 32, o_valid = o_lr + 2 * CH * Lr * 128;
+                    const size_t slot_bytes = (o_valid + CH + 127) & ~(size_t)127;
+                    const bp::OutLayout l{CH, c, Lr, o_pts};
+                    CHECK(l.o_pts() == o_pts && l.o_fe() == o_fe && l.o_lr() == o_lr && l.o_valid() == o_valid,
+                          "output offsets cap=%zu c=%zu Lr=%zu", CH, c, Lr);
+                    CHECK(l.slot_bytes() == slot_bytes && l.end() == o_valid + CH, "output bytes cap=%zu Lr=%zu", CH, Lr);
+                    CHECK(l.used() == o_valid + c - o_pts, "output D2H bytes");
+                    uint8_t* base = (uint8_t*)malloc(slot_bytes);
+                    hipbp_proof_out o;
+                    l.view(base, &o);
+                    std::vector<Region> rg = {{o.V, c * 128}, {o.A, c * 128}, {o.S, c * 128}, {o.T1, c * 128},
+                                              {o.T2, c * 128}, {o.taux, c * 32}, {o.mu, c * 32}, {o.t, c * 32},
+                                              {o.c, c * 32}, {o.x, c * 32}, {o.a, c * 32}, {o.b, c * 32}};
+                    std::vector<size_t> want;
+                    for (size_t i = 0; i < 5; i++) want.push_back(o_pts + i * c * 128);
+                    for (size_t i = 0; i < 7; i++) want.push_back(o_fe + i * c * 32);
+                    if (Lr) {
+                        rg.push_back({o.L, c * Lr * 128});
+                        rg.push_back({o.R, c * Lr * 128});
+                        want.push_back(o_lr);
+                        want.push_back(o_lr + c * Lr * 128);
+                    } else {
+                        CHECK(!o.L && !o.R, "L, R must be null at Lr = 0");
+                    }
+                    rg.push_back({o.valid, c});
+                    want.push_back(o_valid);
+                    CHECK(check_regions(base, rg, want) <= slot_bytes, "output regions leave the slot");
+                    // the packed arrays stay inside their cap-sized regions
+                    CHECK(5 * c * 128 <= o_fe - o_pts && 7 * c * 32 <= o_lr - o_fe && 2 * c * Lr * 128 <= o_valid - o_lr,
+                          "packed arrays leave their regions");
+                    free(base);
+                }
+        }
+}
+
+// c proofs of one shape, every field and vector filled with distinct bytes
+struct Proofs {
+    std::vector<RangeProof> rp;
+    std::vector<ge25519> V;
+    std::vector<std::vector<fe25519>> a, b;
+    std::vector<std::vector<ge25519>> L, R;
+    Proofs(size_t c, size_t abl, size_t Lr, size_t n) : rp(c), V(c), a(c), b(c), L(c), R(c) {
+        for (size_t k = 0; k < c; k++) {
+            fill(&rp[k], sizeof(RangeProof));
+            fill(&V[k], sizeof(ge25519));
+            a[k].resize(abl); b[k].resize(abl); L[k].resize(Lr); R[k].resize(Lr);
+            fill(a[k].data(), abl * 32); fill(b[k].data(), abl * 32);
+            fill(L[k].data(), Lr * 128); fill(R[k].data(), Lr * 128);
+            InnerProductProof& ip = rp[k].ip_proof;
+            ip.n = n;
+            ip.a = FieldVector{a[k].data(), abl};
+            ip.b = FieldVector{b[k].data(), abl};
+            ip.L = PointVector{Lr ? L[k].data() : nullptr, Lr};
+            ip.R = PointVector{Lr ? R[k].data() : nullptr, Lr};
+            ip.L_len = Lr;
+        }
+    }
+};
+
+static void pack_view() {
+    const size_t cs[] = {1, 2, 3, 5}, abls[] = {1, 2, 3}, Lrs[] = {0, 1, 6};
+    for (size_t c : cs)
+        for (size_t abl : abls)
+            for (size_t Lr : Lrs)
+                for (int range = 1; range >= 0; range--) {   // 0: the inner-product-only staging (no RangeProof, no V)
+                    const Proofs P(c, abl, Lr, (size_t)1 << Lr);
+                    const bp::ChunkLayout l{c, abl, Lr};
+                    std::vector<uint8_t> buf(l.bytes(), 0xAA);   // exactly the chunk: an overrun is the sanitizer's
+                    for (size_t k = 0; k < c; k++)
+                        l.pack(buf.data(), k, P.rp[k].ip_proof, range ? &P.rp[k] : nullptr, range ? &P.V[k] : nullptr);
+                    hipbp_proof_batch b;
+                    l.view(buf.data(), &b);
+                    for (size_t k = 0; k < c; k++) {
+                        const RangeProof& p = P.rp[k];
+                        if (range) {
+                            CHECK(same(b.V[k], P.V[k]) && same(b.A[k], p.A) && same(b.S[k], p.S) && same(b.T1[k], p.T1) &&
+                                  same(b.T2[k], p.T2) && same(b.t[k], p.t), "range fields of proof %zu", k);
+                        } else {
+                            CHECK(all_zero(&b.V[k], 128) && all_zero(&b.A[k], 128) && all_zero(&b.S[k], 128) &&
+                                  all_zero(&b.T1[k], 128) && all_zero(&b.T2[k], 128) && all_zero(&b.t[k], 32),
+                                  "absent range fields of proof %zu must be zero", k);
+                        }
+                        CHECK(same(b.c[k], p.ip_proof.c) && same(b.x[k], p.ip_proof.x), "c, x of proof %zu", k);
+                        for (size_t j = 0; j < abl; j++)
+                            CHECK(same(b.a[k * abl + j], P.a[k][j]) && same(b.b[k * abl + j], P.b[k][j]), "a, b of proof %zu", k);
+                        for (size_t j = 0; j < Lr; j++)
+                            CHECK(same(b.L[k * Lr + j], P.L[k][j]) && same(b.R[k * Lr + j], P.R[k][j]), "L, R of proof %zu", k);
+                    }
+                }
+}
+
+static void unpack() {
+    const size_t shapes[][3] = {{4, 4, 3}, {5, 3, 3}, {3, 3, 0}, {4, 2, 0}, {2, 1, 6}, {16, 7, 1}};   // cap, c, Lr
+    for (auto& sh : shapes)
+        for (int with_lead = 0; with_lead < 2; with_lead++) {
+            const size_t cap = sh[0], c = sh[1], Lr = sh[2], n = (size_t)1 << Lr;
+            const bp::OutLayout l{cap, c, Lr, with_lead ? 2 * cap * 32 : 0};
+            std::vector<uint8_t> buf(l.slot_bytes(), 0xAA);
+            hipbp_proof_out o;
+            l.view(buf.data(), &o);
+            // the source pattern, proof by proof, written through the view
+            const Proofs P(c, 1, Lr, n);
+            std::vector<fe25519> a(c), b(c);
+            for (size_t k = 0; k < c; k++) {
+                const RangeProof& p = P.rp[k];
+                o.V[k] = p.V; o.A[k] = p.A; o.S[k] = p.S; o.T1[k] = p.T1; o.T2[k] = p.T2;
+                o.taux[k] = p.taux; o.mu[k] = p.mu; o.t[k] = p.t; o.c[k] = p.ip_proof.c; o.x[k] = p.ip_proof.x;
+                o.a[k] = P.a[k][0]; o.b[k] = P.b[k][0];
+                for (size_t j = 0; j < Lr; j++) { o.L[k * Lr + j] = P.L[k][j]; o.R[k * Lr + j] = P.R[k][j]; }
+                o.valid[k] = k % 3 != 1;   // proofs 1, 4, .. are refused
+            }
+            for (size_t k = 0; k < c; k++) {
+                const RangeProof& p = P.rp[k];
+                RangeProof got;
+                memset(&got, 0xFF, sizeof got);
+                const int v = l.unpack(buf.data(), k, n, got);
+                CHECK(v == (k % 3 != 1 ? 1 : 0), "unpack verdict of proof %zu: %d", k, v);
+                CHECK(same(got.V, p.V) && same(got.A, p.A) && same(got.S, p.S) && same(got.T1, p.T1) && same(got.T2, p.T2) &&
+                      same(got.taux, p.taux) && same(got.mu, p.mu) && same(got.t, p.t), "head of proof %zu", k);
+                const InnerProductProof& ip = got.ip_proof;
+                if (v != 1) {
+                    CHECK(all_zero(&ip, sizeof ip), "a refused proof's ip_proof must be all zero");
+                    continue;
+                }
+                CHECK(ip.n == n && ip.a.length == 1 && ip.b.length == 1 && ip.L.length == Lr && ip.R.length == Lr &&
+                      ip.L_len == Lr, "lengths of proof %zu", k);
+                CHECK(ip.a.elements && ip.b.elements && ip.L.elements && ip.R.elements, "vectors of proof %zu", k);
+                CHECK(same(ip.c, p.ip_proof.c) && same(ip.x, p.ip_proof.x) && same(*ip.a.elements, P.a[k][0]) &&
+                      same(*ip.b.elements, P.b[k][0]), "c, x, a, b of proof %zu", k);
+                for (size_t j = 0; j < Lr; j++)
+                    CHECK(same(ip.L.elements[j], P.L[k][j]) && same(ip.R.elements[j], P.R[k][j]), "L, R of proof %zu", k);
+                free(ip.a.elements); free(ip.b.elements); free(ip.L.elements); free(ip.R.elements);
+            }
+        }
+}
+
+template <size_t N>
+static void check_table(const char* what, const size_t (&got)[N], const std::vector<size_t>& want, size_t want_sum) {
+    CHECK(want.size() == N, "%s: %zu buffers, want %zu", what, N, want.size());
+    size_t sum = 0;
+    for (size_t i = 0; i < N && i < want.size(); i++) {
+        CHECK(got[i] == want[i], "%s buffer %zu: %zu bytes, want %zu", what, i, got[i], want[i]);
+        sum += got[i];
+    }
+    CHECK(sum == want_sum, "%s: %zu bytes in all, want %zu", what, sum, want_sum);
+}
+
+static void tables() {
+    using namespace bp;
+    const size_t bins = MSM_BINS;
+    const size_t Bn[][2] = {{1, 1}, {3, 8}, {5, 64}, {2, 128}, {2, 4096}};
+    for (auto& bn : Bn) {
+        const size_t B = bn[0], n = bn[1];
+        for (int sort = 0; sort < 2 && n <= 128; sort++) {
+            const size_t cap = B * (4 * n + 4);
+            size_t sz[PB_COUNT];
+            prove_sizes(B, n, sort != 0, sz);
+            CHECK(prove_cap(B, n) == cap, "prover cap");
+            // by name, then the whole table in the order of the issue's list
+            CHECK(sz[PB_PS] == B * 4 * n * 32 && sz[PB_PTERM] == cap * 128 && sz[PB_CHAIN] == B * 4 * 128 &&
+                  sz[PB_PTS] == B * 5 * 128 && sz[PB_ST] == B * 8 * 32 && sz[PB_TSC] == B * 4 * 32 && sz[PB_TT] == B * 4 * 128 &&
+                  sz[PB_ACUR] == B * n * 32 && sz[PB_BCUR] == B * n * 32 && sz[PB_ISCAL] == B * 2 * n * 32 &&
+                  sz[PB_CSC] == B * 2 * 32 && sz[PB_ITERM] == B * (2 * n + 2) * 128 && sz[PB_MISC] == B * 4 * 32 &&
+                  sz[PB_VALID] == B && sz[PB_LIST] == 2 * cap * 4 && sz[PB_CNT] == 8 && sz[PB_CTAB] == 2 * n * 128 &&
+                  sz[PB_SLIST] == (sort ? cap * 4 : 0) && sz[PB_SBINS] == (sort ? bins * 4 : 0), "prover buffers by name");
+            const size_t sum = B * (8 * n + 18) * 32 + (cap + B * (2 * n + 15) + 2 * n) * 128 + B + 2 * cap * 4 + 8 +
+                               (sort ? cap * 4 + bins * 4 : 0);
+            check_table("prover", sz,
+                        {B * 4 * n * 32, cap * 128, B * 4 * 128, B * 5 * 128, B * 8 * 32, B * 4 * 32, B * 4 * 128, B * n * 32,
+                         B * n * 32, B * 2 * n * 32, B * 2 * 32, B * (2 * n + 2) * 128, B * 4 * 32, B, 2 * cap * 4, 8,
+                         2 * n * 128, sort ? cap * 4 : 0, sort ? bins * 4 : 0}, sum);
+        }
+        {   // the IPA chunk (here B is Bc)
+            const size_t cap = 2 * n + 2, per_proof = (5 * n + 6) * 32 + (2 * n + 6) * 128 + 2 * cap * 4;
+            size_t sz[IB_COUNT];
+            ipa_sizes(B, n, sz);
+            CHECK(ipa_cap(n) == cap && ipa_per_proof(n) == per_proof, "ipa cap / per_proof");
+            CHECK(sz[IB_A] == B * n * 32 && sz[IB_B] == B * n * 32 && sz[IB_PROD] == B * n * 32 && sz[IB_SC] == B * 2 * n * 32 &&
+                  sz[IB_CSC] == B * 2 * 32 && sz[IB_TERM] == B * 2 * n * 128 && sz[IB_CQ] == B * 2 * 128 &&
+                  sz[IB_CHAIN] == B * 4 * 128 && sz[IB_TR] == B * 32 && sz[IB_UU] == B * 2 * 32 && sz[IB_X] == B * 32 &&
+                  sz[IB_SLIST] == B * cap * 4 && sz[IB_LLIST] == B * cap * 4 && sz[IB_CTL] == (bins + 2) * 4,
+                  "ipa buffers by name");
+            check_table("ipa", sz,
+                        {B * n * 32, B * n * 32, B * n * 32, B * 2 * n * 32, B * 2 * 32, B * 2 * n * 128, B * 2 * 128, B * 4 * 128,
+                         B * 32, B * 2 * 32, B * 32, B * cap * 4, B * cap * 4, (bins + 2) * 4}, B * per_proof + (bins + 2) * 4);
+        }
+        for (int mode = 0; mode < 3; mode++)
+            for (size_t Lb : {(size_t)0, (size_t)3}) {
+                const size_t Lc = Lb ? Lb : 1, m2 = mode == 2 ? B : 0;
+                size_t sz[B_COUNT];
+                verify_sizes(B, n, Lb, mode, sz);
+                CHECK(sz[B_SG] == B * 32 && sz[B_SH] == B * n * 32 && sz[B_SC] == B * 4 * 32 && sz[B_U] == B * Lc * 32 &&
+                      sz[B_UINV] == B * Lc * 32 && sz[B_IPOK] == B && sz[B_MSM_PTS] == B * 2 * n * 128 &&
+                      sz[B_MSM_PART] == B * 2 * 128 && sz[B_TERMS] == B * 4 * 128 && sz[B_FOLD0] == B * 2 * n * 128 &&
+                      sz[B_FOLD1] == B * 2 * n * 128 && sz[B_FIN] == B * 2 * 128 && sz[B_PIN] == B * 128 &&
+                      sz[B_PSC] == m2 * 8 * 32 && sz[B_PTERM] == m2 * 8 * 128 && sz[B_LR] == m2 * 2 * 128 && sz[B_CHAL] == m2 * 32 &&
+                      sz[B_M3] == m2 * 2 * 128 && sz[B_RFLAGS] == m2 && sz[B_PBASE] == m2 * 3 * 128 && sz[B_PERM] == 0,
+                      "verify buffers by name, mode %d", mode);
+                size_t sum = 0;
+                for (size_t s : sz) sum += s;
+                CHECK(sum == B * ((5 + n + 2 * Lc) * 32 + 1 + (6 * n + 9) * 128) + m2 * (9 * 32 + 15 * 128 + 1),
+                      "verify slot: %zu bytes in all, mode %d", sum, mode);
+            }
+    }
+    const size_t nc[][2] = {{1, 1}, {300, 1}, {256, 3}, {257, 2}, {4096, 5}};
+    for (auto& x : nc) {
+        const size_t n = x[0], count = x[1], tot = n * count, nb = count * ((n + 255) / 256);
+        size_t sz[MB_COUNT];
+        msm_sizes(n, count, sz);
+        CHECK(sz[MB_TERMS] == tot * 128 && sz[MB_ROOT0] == nb * 128 && sz[MB_ROOT1] == nb * 128 && sz[MB_TREE0] == 0 &&
+              sz[MB_TREE1] == 0 && sz[MB_ORDER] == tot * 4 && sz[MB_BINS] == bins * 4, "msm buffers by name");
+        check_table("msm", sz, {tot * 128, nb * 128, nb * 128, 0, 0, tot * 4, bins * 4}, tot * 132 + nb * 256 + bins * 4);
+        tree_sizes(n, sz);
+        const size_t tb = (n + 255) / 256 * 128;
+        check_table("tree", sz, {0, 0, 0, tb, tb, 0, 0}, 2 * tb);
+    }
+}
+
+int main() {
+    offsets();
+    pack_view();
+    unpack();
+    tables();
+    std::printf("%llu %llu\n", checks, fails);
+    return fails ? 1 : 0;
+}

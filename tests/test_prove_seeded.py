@@ -218,3 +218,48 @@ def test_argument_errors_write_nothing(bp, T, gens_for):
         bp.batch_generate_range_proof_host(v, gamma, 8, Gn, Hn, gn, hn, SEED[:31])
     with pytest.raises(bp.BulletproofError):
         bp.batch_generate_range_proof_host(v, gamma, 3, Gn, Hn, gn, hn, SEED)
+
+
+def test_release_frees_every_workspace_of_a_stream(bp, T, gens_for, oracle):
+    """hipbp_release_stream_workspaces over a stream that used every per-stream workspace: on one
+    fresh stream, two rounds of the explicit prover, the seeded prover, batch_inner_product_prove
+    (B = 3: two chunks, so the side stream and its events exist), batch_range_proof_verify (a cached
+    pipeline), msm (n = 300), then the release.  Round 2, on rebuilt workspaces, gives round 1's bits;
+    the three proofs verify.  Inputs: inputs(3, 8, default_rng(0)), the first seed for which the CPU
+    restatement of the reference's prover and verifier accepts all three proofs (checked here too)."""
+    import torch
+    n, B = 8, 3
+    rng = np.random.default_rng(0)
+    v, gamma = inputs(B, n, rng)
+    Gn, Hn, gn, hn = gens_for(n)
+    G, H, g, h = T(Gn), T(Hn), T(gn), T(hn)
+    vd, gd = T(v), T(gamma)
+    sc = {k: T(x) for k, x in ref.derive(SEED, v, gamma, 0, n).items()}
+    ia, ib = (T(rng.integers(0, 2**63, (B, n, 4), dtype=np.uint64)) for _ in range(2))
+    ic = T(rng.integers(0, 2**63, (B, 4), dtype=np.uint64))
+    ms, mP = T(rng.integers(0, 2**63, (300, 4), dtype=np.uint64)), T(oracle.base_points(300, 21))
+    st = torch.cuda.Stream(G.device)
+    rounds = []
+    for _ in range(2):
+        ok = torch.zeros(B, dtype=torch.uint8, device=G.device)
+        m = torch.zeros(16, dtype=torch.int64, device=G.device)
+        torch.cuda.synchronize()
+        o0 = bp.batch_generate_range_proof(n, vd, gd, sc["sL"], sc["sR"], sc["rnd"], G, H, g, h, stream=st)
+        o1 = bp.batch_generate_range_proof_seeded(n, vd, gd, SEED, G, H, g, h, stream=st)
+        ip = bp.batch_inner_product_prove(n, ia, ib, ic, G, H, h, stream=st)
+        bp.batch_range_proof_verify(bp.RangeProofBatch(n, **{k: o0[k] for k in bp.RangeProofBatch.FIELDS}), G, H, g, h, ok,
+                                    stream=st)
+        bp.msm(m, ms, mP, stream=st)
+        bp.release_stream_workspaces(st)   # waits for st first
+        rounds.append([o0[k] for k in KEYS] + [o1[k] for k in KEYS] +
+                      [ip[k] for k in ("a", "b", "c", "x", "c_final", "L", "R")] + [ok, m])
+    for k, (a, b) in enumerate(zip(*rounds)):
+        assert torch.equal(a, b), k
+    same(o0, o1)
+    assert rounds[1][-2].cpu().numpy().tolist() == [1, 1, 1]
+    d = {k: o0[k].cpu().numpy().view(np.uint64) for k in KEYS if k != "valid"}
+    for p in range(B):
+        head = np.concatenate([d[k][p] for k in ("V", "A", "S", "T1", "T2", "taux", "mu", "t", "c", "x")])
+        assert oracle.cuda_range_proof_verify(head, d["V"][p], n, d["a"][p], d["b"][p], d["L"][p], d["R"][p],
+                                              Gn, Hn, gn, hn)[0], p
+    bp.release_stream_workspaces(torch.cuda.Stream(G.device))   # a stream that never ran anything
