@@ -19,7 +19,7 @@
 
 #include "../../include/cudabulletproof_hip.h"
 #include "bp_tick_plan.h"
-#include "bp_layout.h"
+#include "bp_buf.h"
 #include "ge25519_dev.h"
 #include "bp_prove_seed.h"
 
@@ -51,45 +51,9 @@ thread_local std::string g_err;
         }                                                                                     \
     } while (0)
 
-// A grow-only device buffer (Buf) or pinned host staging buffer (PinnedBuf).  need() frees the old
-// allocation when it grows: what must be drained first is each call site's own rule.
-template <bool PINNED>
-struct GrowBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    static hipError_t free_(void* q) { return PINNED ? hipHostFree(q) : hipFree(q); }
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) {
-            hipError_t e = free_(p);
-            if (e != hipSuccess) return e;
-            p = nullptr;
-            cap = 0;
-        }
-        hipError_t e = PINNED ? hipHostMalloc(&p, bytes) : hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    // frees the buffer; the pointer is dropped even if the free fails (nothing is left to free twice)
-    hipError_t release() {
-        hipError_t e = p ? free_(p) : hipSuccess;
-        p = nullptr;
-        cap = 0;
-        return e;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
-using Buf = GrowBuf<false>;
-using PinnedBuf = GrowBuf<true>;
-// every buffer of a workspace grown to its table's size (bp_layout.h)
-template <size_t N>
-hipError_t need_all(Buf (&b)[N], const size_t (&sz)[N]) {
-    for (size_t i = 0; i < N; i++) {
-        hipError_t e = b[i].need(sz[i]);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
+using bp::Buf;
+using bp::PinnedBuf;
+using bp::need_all;
 
 // HIP-event timing of the verify pipeline's kernels (bench.py's live roofline numbers).
 struct EventTimer {
@@ -159,6 +123,7 @@ struct StreamWs {
     Buf ipa[2][bp::IB_COUNT];
     hipStream_t ipa_side = nullptr;
     hipEvent_t ipa_ev[2] = {};   // [0] the caller's stream at entry, [1] the side stream's last chunk done
+    bp::PipPair pip;             // Pippenger MSM (hipbp_msm_pippenger*): both parts' buffers and its side stream
     std::map<std::pair<int, int>, Pipeline*> pipes;   // one-shot verify pipelines, per (n, mode)
     hipError_t release(hipError_t first);
 };
@@ -600,6 +565,12 @@ hipError_t StreamWs::release(hipError_t first) {
     for (hipEvent_t ev : ipa_ev)
         if (ev) keep(hipEventDestroy(ev));
     if (ipa_side) keep(hipStreamDestroy(ipa_side));
+    if (pip.side) keep(hipStreamSynchronize(pip.side));
+    for (auto* part : {&pip.hi, &pip.lo})
+        for (auto& b : *part) keep(b.release());
+    for (hipEvent_t ev : pip.ev)
+        if (ev) keep(hipEventDestroy(ev));
+    if (pip.side) keep(hipStreamDestroy(pip.side));
     for (auto& kv : pipes) {
         kv.second->release();
         delete kv.second;
@@ -869,8 +840,8 @@ int hipbp_msm_pippenger_batch(ge25519* results, const fe25519* scalars, const ge
         return HIPBP_ERR_ARG;
     }
     std::lock_guard<std::mutex> lk(e->mu);
-    BP_RET_ON(bp::msm_pippenger((bp::ge*)results, (const bp::fe*)scalars, (const bp::ge*)points, n, count, window_bits,
-                                e->dtab, pick(stream)));
+    BP_RET_ON(bp::msm_pippenger(e->streams[pick(stream)].pip, (bp::ge*)results, (const bp::fe*)scalars,
+                                (const bp::ge*)points, n, count, window_bits, e->dtab, pick(stream)));
     return HIPBP_OK;
 }
 
@@ -889,14 +860,15 @@ int hipbp_msm_pippenger_windows(ge25519* window_sums, const fe25519* scalars, co
     if (!window_sums || !scalars || !points) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     if (n * (size_t)(w_end - w_begin) > 0x7FFFFFFFull) { g_err = "pippenger: n * windows too large"; return HIPBP_ERR_ARG; }
     std::lock_guard<std::mutex> lk(e->mu);
-    BP_RET_ON(bp::msm_pippenger_windows((bp::ge*)window_sums, (const bp::fe*)scalars, (const bp::ge*)points, n,
-                                        window_bits, w_begin, w_end, e->dtab, pick(stream)));
+    BP_RET_ON(bp::msm_pippenger_windows(e->streams[pick(stream)].pip, (bp::ge*)window_sums, (const bp::fe*)scalars,
+                                        (const bp::ge*)points, n, window_bits, w_begin, w_end, e->dtab, pick(stream)));
     return HIPBP_OK;
 }
 
 // Frees every per-stream workspace the engine keeps for `stream` on the current device (canonical
-// MSM / point-tree buffers, prover buffers, IPA prover pair, one-shot verify pipelines, Pippenger pair),
-// after waiting for the stream.  A later call on that stream builds them again.
+// MSM / point-tree buffers, prover buffers, IPA prover pair, Pippenger pair, one-shot verify pipelines):
+// the stream's one record, after waiting for the stream (and, in the record's release, for the two
+// pairs' side streams).  A later call on that stream builds them again.
 int hipbp_release_stream_workspaces(void* stream) {
     BP_ENGINE_OR_RET(e);
     hipStream_t s = (hipStream_t)stream;
@@ -908,8 +880,6 @@ int hipbp_release_stream_workspaces(void* stream) {
         first = it->second.release(first);
         e->streams.erase(it);
     }
-    const hipError_t pr = bp::pippenger_release(s);
-    if (first == hipSuccess) first = pr;
     if (first != hipSuccess) {
         g_err = std::string("release_stream_workspaces: ") + hipGetErrorString(first);
         return HIPBP_ERR_DEVICE;

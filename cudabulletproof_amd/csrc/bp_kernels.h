@@ -254,14 +254,14 @@ void launch_msm_points(ge* pts, const fe* scal, const ge* P, size_t m, uint32_t*
 void launch_tree(ge* out, const ge* in, int S, size_t m, hipStream_t s);
 void launch_ops_scan(unsigned* bins, int longest_first, hipStream_t s);   // bins -> start offsets
 // Pippenger bucket MSM (bp_pippenger.hip; hipbp_msm_pippenger), 4 <= c <= 12
-// count MSMs over the same n points: results[m] = MSM(scal[m n .. m n + n), P)
-hipError_t msm_pippenger(ge* result, const fe* scal, const ge* P, size_t n, size_t count, int c, const ge* dtab,
-                         hipStream_t s);
-hipError_t msm_pippenger_windows(ge* Sw, const fe* scal, const ge* P, size_t n, int c, int w0, int w1,
+// count MSMs over the same n points: results[m] = MSM(scal[m n .. m n + n), P).  pp: stream s's pair
+// (bp_buf.h), used under its engine's lock.
+struct PipPair;
+hipError_t msm_pippenger(PipPair& pp, ge* result, const fe* scal, const ge* P, size_t n, size_t count, int c,
+                         const ge* dtab, hipStream_t s);
+hipError_t msm_pippenger_windows(PipPair& pp, ge* Sw, const fe* scal, const ge* P, size_t n, int c, int w0, int w1,
                                  const ge* dtab, hipStream_t s);
 hipError_t pippenger_horner(ge* result, const ge* Sw, size_t count, int c, hipStream_t s);
-// Frees the (device, stream) Pippenger workspaces of stream s (after waiting for its work).
-hipError_t pippenger_release(hipStream_t s);
 
 
 

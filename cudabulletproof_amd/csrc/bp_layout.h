@@ -243,4 +243,73 @@ inline void tree_sizes(size_t n, size_t (&sz)[MB_COUNT]) {
     sz[MB_TREE0] = sz[MB_TREE1] = (n + 255) / 256 * GE;   // tree ping-pong
 }
 
+// The Pippenger bucket MSM (bp_pippenger.hip).  Its kernels and the shape share these:
+constexpr int PTPB = 256;                // threads per block
+constexpr int PM = 16;                   // buckets per chunk
+constexpr int SCAN_PER = 4;              // buckets per thread of the layout scans
+constexpr int SCAN_BLK = PTPB * SCAN_PER;
+constexpr uint32_t BID_PIECE = 4096;     // list elements per k_pip_bidfill wave
+// One part of a call: windows [w0, w1) of `count` MSMs over n points, c-bit digits.  force16:
+// HIPBP_PIP_KEYS16; tail_layer: HIPBP_PIP_TAIL_LAYER, clamped to 1 .. 8.
+struct PipShape {
+    size_t n, count;
+    int c, w0, Wp;         // Wp: the part's windows
+    size_t W, NB, nb, N;   // virtual windows (the part's windows of every MSM), buckets per window, buckets, keys
+    size_t NC;             // chunks per window
+    int ib;                // bits of the point index in a 32-bit key
+    bool k32;              // 32-bit keys (digit << ib | i), no values; else 16-bit digit keys and values
+    int levels, steps, T;  // worst-case tree depth (a bucket list is at most n long), two levels per step;
+                           // layouts 0 .. steps, then the start layer T
+    unsigned nparts;       // scan blocks per layer
+    size_t tot0, qcap;     // step 0 reads <= N + 3 nb padded positions and writes a quarter of them (+ padding)
+    size_t nbq;            // bidfill queue capacity (further pieces of long lists)
+    int TT;                // the LDS tail takes over at layer TT (0: none)
+};
+inline PipShape pip_shape(size_t n, size_t count, int c, int w0, int w1, bool force16, int tail_layer) {
+    PipShape s;
+    s.n = n; s.count = count; s.c = c; s.w0 = w0;
+    s.Wp = w1 - w0;
+    s.W = (size_t)s.Wp * count;
+    s.NB = (size_t)1 << c; s.nb = s.W * s.NB; s.N = s.W * n; s.NC = s.NB / PM;
+    s.ib = 0;
+    while (s.ib < 32 && ((size_t)1 << s.ib) < n) s.ib++;
+    s.k32 = c + s.ib <= 32 && !force16;
+    s.levels = 1;
+    while (s.levels < 31 && ((size_t)1 << s.levels) < n) s.levels++;
+    s.steps = (s.levels + 1) / 2; s.T = s.steps + 1;
+    s.nparts = (unsigned)((s.nb + SCAN_BLK - 1) / SCAN_BLK);
+    s.tot0 = s.N + 3 * s.nb; s.qcap = s.tot0 / 4 + 4 * s.nb;
+    s.nbq = s.N / BID_PIECE + 1;
+    s.TT = s.steps > tail_layer ? tail_layer : 0;
+    return s;
+}
+// The part's workspace (PipWs).  lay: LEN | PAD | OFF, T + 1 layers of nb each.  Wtot: all the windows
+// of an MSM where this workspace also holds the whole call's window sums and the top part's Horner
+// value (msm_pippenger's top part), else 0.  sort_temp: rocPRIM's scratch, from its size query.
+#define BP_PIP_BUFS(X)                                                \
+    X(PIP_KEYS_IN, keys_in, void, s.N * (s.k32 ? 4 : 2))              \
+    X(PIP_KEYS, keys, void, s.N * (s.k32 ? 4 : 2))                    \
+    X(PIP_VALS, vals, uint32_t, s.k32 ? 0 : s.N * 4)                  \
+    X(PIP_START, start, uint32_t, s.nb * 4)                           \
+    X(PIP_LEN0, len[0], uint32_t, s.nb * 4)                           \
+    X(PIP_LEN1, len[1], uint32_t, s.nb * 4)                           \
+    X(PIP_LAY, lay, uint32_t, (size_t)3 * (s.T + 1) * s.nb * 4)       \
+    X(PIP_PART, part, uint32_t, (size_t)(s.T + 1) * s.nparts * 4)     \
+    X(PIP_BID0, bid[0], uint32_t, s.tot0 * 4)                         \
+    X(PIP_BID1, bid[1], uint32_t, s.qcap * 4)                         \
+    X(PIP_Q0, Q[0], ge, s.qcap * GE)                                  \
+    X(PIP_Q1, Q[1], ge, s.qcap * GE)                                  \
+    X(PIP_V, V, ge, s.W * s.NC * GE)                                  \
+    X(PIP_S, S, ge, s.nb * GE)                                        \
+    X(PIP_MAXLEN, maxlen, unsigned, 3 * U32)                          \
+    X(PIP_TAILQ, tailq, uint32_t, s.TT ? s.nb * U32 : 0)              \
+    X(PIP_BQ, bq, uint2, s.nbq * 8)                                   \
+    X(PIP_SW, Sw, ge, s.count * Wtot * GE)                            \
+    X(PIP_TMID, Tmid, ge, Wtot ? s.count * GE : 0)                    \
+    X(PIP_TEMP, temp, void, sort_temp)
+enum PipBuf { BP_PIP_BUFS(BP_BUF_ID) PIP_COUNT };
+inline void pip_sizes(const PipShape& s, size_t Wtot, size_t sort_temp, size_t (&sz)[PIP_COUNT]) {
+    BP_PIP_BUFS(BP_BUF_SIZE)
+}
+
 }  // namespace bp

@@ -26,18 +26,15 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 
-#include "bp_kernels.h"
+#include "bp_buf.h"
 #include "ge25519_dev.h"
 #include "ge25519_quad.h"
 
 namespace bp {
 
 namespace {
-constexpr int PTPB = 256;
-constexpr int PM = 16;   // buckets per chunk
+// (PTPB, PM, SCAN_PER, SCAN_BLK, BID_PIECE: bp_layout.h, with the shape that is sized by them)
 
 // Division of 32-bit values by a run-time invariant d >= 1 (round-up multiplier, Granlund and
 // Montgomery): q = (t + ((x - t) >> s1)) >> s2 with t = umulhi(m, x), exact for every 32-bit x.
@@ -173,7 +170,6 @@ __global__ __launch_bounds__(HIST_TPB) void k_pip_hist(const KT* __restrict__ ke
 // carries), so lists are padded to a multiple of 4.  bid[pos] = the bucket of element pos (every
 // group head is a real element, so no search is needed).  k_pip_len0: the longest list (one atomic per wave), and the counts in sorted order — digit-major, virtual
 // window minor — whose exclusive scan is each bucket's start in the sorted array.
-constexpr uint32_t BID_PIECE = 4096;   // list elements per k_pip_bidfill wave
 __global__ __launch_bounds__(PTPB) void k_pip_len0(const uint32_t* __restrict__ len, uint32_t* cnt_t,
                                                   size_t nb, int c, uint32_t Wv, unsigned* maxlen, ge* S,
                                                   uint2* bq) {
@@ -231,9 +227,6 @@ __device__ __forceinline__ int pip_steps(const unsigned* maxlen) {
 // per layer (blockIdx.y): k_pip_lay_part writes LEN/PAD for SCAN_PER consecutive buckets per
 // thread and one partial sum per block; k_pip_lay_fin adds the partial sums of the blocks before
 // it and scans.
-constexpr int SCAN_PER = 4;
-constexpr int SCAN_BLK = PTPB * SCAN_PER;
-
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -639,36 +632,16 @@ __global__ __launch_bounds__(PTPB) void k_pip_chunks(const ge* __restrict__ Sb, 
     if ((threadIdx.x & 7) == 0) V[g] = r;
 }
 
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) {   // growing: earlier MSMs on this workspace's streams may still read the old buffer
-            hipError_t e = hipDeviceSynchronize();
-            if (e == hipSuccess) e = hipFree(p);
-            if (e != hipSuccess) return e;
-            p = nullptr;
-            cap = 0;
-        }
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    template <typename T> T* as() const { return (T*)p; }
-};
+// One part's buffers as the launches take them (a field per line of BP_PIP_BUFS, bp_layout.h).  The
+// keys are uint32_t (PipShape::k32) or uint16_t: cast where they are sorted and launched.
 struct PipWs {
-    DBuf keys_in, keys, vals, temp, start, len[2], lay, bq, bid[2], Q[2], S, V, Sw, Tmid, maxlen, part, tailq;
-    hipStream_t side = nullptr;           // the Horner chain's stream
-    hipEvent_t ev[4] = {};   // [1] top half's buckets done, [2] bottom half done, [3] chain done
+    void *keys_in, *keys, *temp;
+    uint32_t *vals, *start, *len[2], *lay, *part, *bid[2], *tailq;
+    ge *Q[2], *V, *S, *Sw, *Tmid;
+    unsigned* maxlen;
+    uint2* bq;
+    size_t temp_bytes;   // of temp, as rocPRIM's size query gave it
 };
-// Workspaces per (device, stream): torch's default stream is handle 0 on every device, so the
-// stream alone does not identify a workspace.  Each pair holds the top and bottom part's
-// workspaces.  g_pip_mu guards the map (engines of different devices hold different locks);
-// a workspace itself is used only under its device's engine lock.
-struct PipPair { PipWs hi, lo; };
-std::map<std::pair<int, hipStream_t>, PipPair*> g_pip;
-std::mutex g_pip_mu;
 
 inline unsigned nb_of(size_t items) { return (unsigned)((items + PTPB - 1) / PTPB); }
 }  // namespace
@@ -696,250 +669,182 @@ static hipError_t pip_sort32(void* temp, size_t& tb, const uint32_t* kin, uint32
                              hipStream_t s) {
     return rocprim::radix_sort_keys<PipSortCfg>(temp, tb, kin, kout, (unsigned)N, (unsigned)ib, (unsigned)(ib + c), s);
 }
+// the part's sort, or with temp = null rocPRIM's size query (which sets tb and reads nothing)
+static hipError_t pip_sort_part(const PipShape& sh, void* temp, size_t& tb, const void* kin, void* kout, uint32_t* vout,
+                                hipStream_t s) {
+    if (sh.k32) return pip_sort32(temp, tb, (const uint32_t*)kin, (uint32_t*)kout, sh.N, sh.ib, sh.c, s);
+    return pip_sort(temp, tb, (const uint16_t*)kin, (uint16_t*)kout, vout, sh.N, sh.c, s);
+}
 // HIPBP_PIP_KEYS16=1 forces the 16-bit-key path (read per call: tests run both paths in one process)
 static bool pip_force16() {
     const char* e = getenv("HIPBP_PIP_KEYS16");
     return e && e[0] == '1';
 }
 
-// Bucket sums of windows [w0, w1) on stream s, into ws.S (the step that finishes a list writes it).
-static hipError_t pip_buckets(PipWs& ws, const fe* scal, const ge* P, size_t n, size_t count, int c, int w0, int w1,
-                              hipStream_t s) {
-    const int Wp = w1 - w0;
-    const size_t W = (size_t)Wp * count;   // virtual windows: the part's windows of every MSM
-    const size_t NB = (size_t)1 << c, nb = W * NB, N = W * n, NC = NB / PM;
-    int ib = 0;   // bits of the point index in a 32-bit key
-    while (ib < 32 && ((size_t)1 << ib) < n) ib++;
-    const bool k32 = c + ib <= 32 && !pip_force16();
-    PIP_RET(ws.keys_in.need(N * (k32 ? 4 : 2)));
-    PIP_RET(ws.keys.need(N * (k32 ? 4 : 2)));
-    if (!k32) PIP_RET(ws.vals.need(N * 4));
-    PIP_RET(ws.start.need(nb * 4));
-    for (int i = 0; i < 2; i++) {
-        PIP_RET(ws.len[i].need(nb * 4));
-    }
-    // the worst-case step count (a bucket list is at most n long); steps past the depth of the
-    // data exit on the device (pip_steps), so nothing here waits for the GPU
-    int levels = 1;
-    while (levels < 31 && ((size_t)1 << levels) < n) levels++;
-    const int steps = (levels + 1) / 2, T = steps + 1;   // layouts 0 .. steps, then the start layer T
-    const unsigned nparts = (unsigned)((nb + SCAN_BLK - 1) / SCAN_BLK);
-    PIP_RET(ws.lay.need((size_t)3 * (T + 1) * nb * 4));
-    PIP_RET(ws.part.need((size_t)(T + 1) * nparts * 4));
-    uint32_t* LEN = ws.lay.as<uint32_t>();
-    uint32_t* PAD = LEN + (size_t)(T + 1) * nb;
-    uint32_t* OFF = PAD + (size_t)(T + 1) * nb;
-    // step 0 reads <= N + 3 nb padded positions and writes a quarter of them (+ padding)
-    const size_t tot0 = N + 3 * nb, qcap = tot0 / 4 + 4 * nb;
-    PIP_RET(ws.bid[0].need(tot0 * 4)); PIP_RET(ws.bid[1].need(qcap * 4));
-    PIP_RET(ws.Q[0].need(qcap * sizeof(ge))); PIP_RET(ws.Q[1].need(qcap * sizeof(ge)));
-    PIP_RET(ws.V.need((size_t)W * NC * sizeof(ge)));
-    PIP_RET(ws.S.need(nb * sizeof(ge)));
-    PIP_RET(ws.maxlen.need(3 * sizeof(unsigned)));
-    const int TL = pip_tail_layer();
-    const int TT = steps > TL ? TL : 0;   // the LDS tail takes over at layer TT (0: none)
-    if (TT) PIP_RET(ws.tailq.need(nb * sizeof(uint32_t)));
-    const size_t nbq = N / BID_PIECE + 1;   // bidfill queue capacity (further pieces of long lists)
-    PIP_RET(ws.bq.need(nbq * sizeof(uint2)));
-    size_t tb_sort = 0;
-    if (k32)
-        PIP_RET(pip_sort32(nullptr, tb_sort, ws.keys_in.as<uint32_t>(), ws.keys.as<uint32_t>(), N, ib, c, s));
-    else
-        PIP_RET(pip_sort(nullptr, tb_sort, ws.keys_in.as<uint16_t>(), ws.keys.as<uint16_t>(), ws.vals.as<uint32_t>(),
-                         N, c, s));
-    PIP_RET(ws.temp.need(tb_sort));
-
-    const FastDiv fn = fastdiv_make((uint32_t)n);
-    // keys_in rows start 8-byte (16-byte) aligned when n % 4 == 0 (DBuf memory)
-    const bool v4 = n % 4 == 0;
-    const unsigned kgrid = nb_of(v4 ? count * n / 4 : count * n);
-    if (k32 && v4)
-        k_pip_keys<4, uint32_t><<<kgrid, PTPB, 0, s>>>(scal, fn, (uint32_t)count, c, ib, w0, Wp, ws.keys_in.as<uint32_t>(),
-                                                        ws.len[0].as<uint32_t>(), nb, ws.maxlen.as<unsigned>());
-    else if (k32)
-        k_pip_keys<1, uint32_t><<<kgrid, PTPB, 0, s>>>(scal, fn, (uint32_t)count, c, ib, w0, Wp, ws.keys_in.as<uint32_t>(),
-                                                        ws.len[0].as<uint32_t>(), nb, ws.maxlen.as<unsigned>());
-    else if (v4)
-        k_pip_keys<4, uint16_t><<<kgrid, PTPB, 0, s>>>(scal, fn, (uint32_t)count, c, 0, w0, Wp, ws.keys_in.as<uint16_t>(),
-                                                        ws.len[0].as<uint32_t>(), nb, ws.maxlen.as<unsigned>());
-    else
-        k_pip_keys<1, uint16_t><<<kgrid, PTPB, 0, s>>>(scal, fn, (uint32_t)count, c, 0, w0, Wp, ws.keys_in.as<uint16_t>(),
-                                                        ws.len[0].as<uint32_t>(), nb, ws.maxlen.as<unsigned>());
-    const uint32_t tpw = (uint32_t)((n + HIST_TILE - 1) / HIST_TILE);
-    if (k32)
-        k_pip_hist<uint32_t><<<(unsigned)(W * tpw), HIST_TPB, NB * 4, s>>>(ws.keys_in.as<uint32_t>(), (uint32_t)n, c,
-                                                                           ib, tpw, ws.len[0].as<uint32_t>());
-    else
-        k_pip_hist<uint16_t><<<(unsigned)(W * tpw), HIST_TPB, NB * 4, s>>>(ws.keys_in.as<uint16_t>(), (uint32_t)n, c,
-                                                                           0, tpw, ws.len[0].as<uint32_t>());
-    // the counts in sorted order (transposed), for the start layer
-    k_pip_len0<<<nb_of(nb), PTPB, 0, s>>>(ws.len[0].as<uint32_t>(), ws.len[1].as<uint32_t>(), nb, c, (uint32_t)W,
-                                          ws.maxlen.as<unsigned>(), ws.S.as<ge>(), ws.bq.as<uint2>());
-    // every step's layout (LEN, PAD, OFF)[t], t = 0 .. steps, and OFF[T] = the sorted-order starts
-    k_pip_lay_part<<<dim3(nparts, T + 1), PTPB, 0, s>>>(ws.len[0].as<uint32_t>(), ws.len[1].as<uint32_t>(), T, nb,
-                                                        LEN, PAD, ws.part.as<uint32_t>(), nparts, TT,
-                                                        ws.tailq.as<uint32_t>(), ws.maxlen.as<unsigned>() + 2);
-    k_pip_lay_fin<<<dim3(nparts, T + 1), PTPB, 0, s>>>(PAD, ws.part.as<uint32_t>(), nparts, nb, OFF);
-    k_pip_start<<<nb_of(nb), PTPB, 0, s>>>(OFF + (size_t)T * nb, nb, c, (uint32_t)W, ws.start.as<uint32_t>());
-    if (k32) {
-        PIP_RET(pip_sort32(ws.temp.p, tb_sort, ws.keys_in.as<uint32_t>(), ws.keys.as<uint32_t>(), N, ib, c, s));
-        k_pip_bidfill<<<nb_of((nb + nbq) * 64), PTPB, 0, s>>>(LEN, OFF, nb, ws.maxlen.as<unsigned>(),
-                                                               ws.bq.as<uint2>(), ws.bid[0].as<uint32_t>());
-    } else {
-        PIP_RET(pip_sort(ws.temp.p, tb_sort, ws.keys_in.as<uint16_t>(), ws.keys.as<uint16_t>(), ws.vals.as<uint32_t>(),
-                         N, c, s));
-        k_pip_bid0<<<nb_of(N), PTPB, 0, s>>>(ws.keys.as<uint16_t>(), ws.vals.as<uint32_t>(), N, fn, c,
-                                             ws.start.as<uint32_t>(), OFF, ws.bid[0].as<uint32_t>());
-    }
-    const uint32_t* keys32 = k32 ? ws.keys.as<uint32_t>() : nullptr;
-    const uint32_t imask = ib >= 32 ? 0xFFFFFFFFu : (uint32_t)((1ull << ib) - 1);
-    // step t: layout t -> t + 1, (bid, data)[t & 1] -> [(t + 1) & 1]
-    // at least nb lanes in every step (step 0 too: when n < 2^c / 4 the padded total is below
-    // 4 nb), so the octet tail path, which takes up to nb / 8 groups, always has its 8 lanes each
-    size_t lanes = std::max((tot0 + 3) / 4, nb);
-    for (int t = 0; t < (TT ? TT + 1 : steps); t++) {
-        const int a = t & 1, b = a ^ 1;
-        const size_t l0 = (size_t)t * nb, l1 = l0 + nb;
-        k_pip_step<<<nb_of(lanes), PTPB, 0, s>>>(t, ws.maxlen.as<unsigned>(), P, fn, keys32, imask,
-                                                  ws.vals.as<uint32_t>(),
-                                                  ws.start.as<uint32_t>(), ws.Q[a].as<ge>(), ws.bid[a].as<uint32_t>(),
-                                                  OFF + l0, LEN + l0, PAD + l0, OFF + l1, ws.Q[b].as<ge>(),
-                                                  ws.bid[b].as<uint32_t>(), ws.S.as<ge>(), nb, lanes, TT ? TT : -1);
-        lanes = lanes / 4 + nb;
-    }
-    if (TT)   // layer TT's lists that need more than one more step (written by step TT - 1 into Q[TT & 1]), in LDS
-        k_pip_tail<<<(unsigned)std::min(nb, (size_t)2048), PTPB, 0, s>>>(
-            ws.tailq.as<uint32_t>(), ws.maxlen.as<unsigned>() + 2, ws.Q[TT & 1].as<ge>(), OFF + (size_t)TT * nb,
-            LEN + (size_t)TT * nb, ws.S.as<ge>());
-    return hipGetLastError();
-}
-
-// Chunks -> window sums of windows [w0, w1) into Sw[w0 .. w1-1], on stream s (latency-bound).
-static hipError_t pip_finish(PipWs& ws, size_t count, int c, int Wtot, int w0, int w1, ge* Sw, const ge* dtab,
-                             hipStream_t s) {
-    const int Wp = w1 - w0, W = Wp * (int)count;
-    const size_t NC = ((size_t)1 << c) / PM;
-    k_pip_chunks<<<nb_of(8 * (size_t)W * NC), PTPB, 0, s>>>(ws.S.as<ge>(), c, W, ws.V.as<ge>(), dtab);
-    k_pip_window<<<W, PTPB, 0, s>>>(ws.V.as<ge>(), (int)NC, Wp, Wtot, w0, Sw);
-    return hipGetLastError();
-}
-
-// The windows run as two halves, top half first, each with its own workspace.  The caller's
-// stream carries the throughput work (sort + bucket trees of both halves, then the bottom half's
-// chunks); a side stream carries the latency-bound chains: the top half's chunks + window trees
-// + its part of the Horner chain (~126 dependent doublings) overlap the bottom half's bucket
-// trees, and only the bottom half's chunks and Horner part remain at the end.  Same values,
-// same bits.
-static hipError_t pip_pair(PipPair** out, hipStream_t s) {
-    int dev = 0;
-    PIP_RET(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_pip_mu);
-    auto key = std::make_pair(dev, s);
-    auto it = g_pip.find(key);
-    if (it != g_pip.end()) { *out = it->second; return hipSuccess; }
-    PipPair* pp = new PipPair();
-    auto fail = [&](hipError_t e) {   // a half-made pair is never cached
-        if (pp->hi.side) (void)hipStreamDestroy(pp->hi.side);
-        for (auto& ev : pp->hi.ev)
-            if (ev) (void)hipEventDestroy(ev);
-        delete pp;
-        return e;
-    };
-    hipError_t e;
-    // a high-priority stream: HIP spreads streams over a few hardware queues, and one that
-    // shared the caller's queue would serialize the chains behind the bottom half again
-    int lo_pr = 0, hi_pr = 0;
-    if ((e = hipDeviceGetStreamPriorityRange(&lo_pr, &hi_pr)) != hipSuccess) return fail(e);
-    if ((e = hipStreamCreateWithPriority(&pp->hi.side, hipStreamNonBlocking, hi_pr)) != hipSuccess) return fail(e);
-    for (auto& ev : pp->hi.ev)
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(e);
-    g_pip[key] = pp;
-    *out = pp;
+// Buffers b grown to part sh's sizes (pip_sizes: Wtot) and viewed as w.  Earlier MSMs on the caller's
+// stream and on the pair's side stream may still read a live buffer, so the whole device is drained,
+// once, before any of them is freed to grow.
+static hipError_t pip_carve(Buf (&b)[PIP_COUNT], const PipShape& sh, size_t Wtot, hipStream_t s, PipWs& w) {
+    w.temp_bytes = 0;
+    PIP_RET(pip_sort_part(sh, nullptr, w.temp_bytes, nullptr, nullptr, nullptr, s));
+    size_t sz[PIP_COUNT];
+    pip_sizes(sh, Wtot, w.temp_bytes, sz);
+    for (int i = 0; i < PIP_COUNT; i++)
+        if (b[i].p && sz[i] > b[i].cap) {
+            PIP_RET(hipDeviceSynchronize());
+            break;
+        }
+    PIP_RET(need_all(b, sz));
+    BP_PIP_BUFS(BP_BUF_FIELD)
     return hipSuccess;
 }
 
-hipError_t msm_pippenger(ge* result, const fe* scal, const ge* P, size_t n, size_t count, int c, const ge* dtab,
-                         hipStream_t s) {
+// The keys of part sh from the scalars, and the bucket sizes from the keys, into len[0].
+template <typename KT>
+static void pip_keys_hist(const PipWs& w, const PipShape& sh, const fe* scal, const FastDiv& fn, hipStream_t s) {
+    // a V = 4 thread stores 4 keys at once: keys_in rows start 8-byte (16-byte) aligned when n % 4 == 0,
+    // the buffer itself being a hipMalloc allocation (aligned to 256 bytes at least)
+    const bool v4 = sh.n % 4 == 0;
+    const int ib = sizeof(KT) == 4 ? sh.ib : 0;
+    auto* const keys = v4 ? &k_pip_keys<4, KT> : &k_pip_keys<1, KT>;
+    keys<<<nb_of(v4 ? sh.count * sh.n / 4 : sh.count * sh.n), PTPB, 0, s>>>(
+        scal, fn, (uint32_t)sh.count, sh.c, ib, sh.w0, sh.Wp, (KT*)w.keys_in, w.len[0], sh.nb, w.maxlen);
+    const uint32_t tpw = (uint32_t)((sh.n + HIST_TILE - 1) / HIST_TILE);
+    k_pip_hist<KT><<<(unsigned)(sh.W * tpw), HIST_TPB, sh.NB * 4, s>>>((const KT*)w.keys_in, (uint32_t)sh.n, sh.c, ib,
+                                                                        tpw, w.len[0]);
+}
+
+// Bucket sums of part sh on stream s, into w.S (the step that finishes a list writes it).  The step
+// count is the worst case; steps past the depth of the data exit on the device (pip_steps), so
+// nothing here waits for the GPU.
+static hipError_t pip_buckets(const PipWs& w, const PipShape& sh, const fe* scal, const ge* P, hipStream_t s) {
+    const size_t nb = sh.nb, N = sh.N;
+    const int c = sh.c, T = sh.T, TT = sh.TT;
+    uint32_t* LEN = w.lay;
+    uint32_t* PAD = LEN + (size_t)(T + 1) * nb;
+    uint32_t* OFF = PAD + (size_t)(T + 1) * nb;
+    const FastDiv fn = fastdiv_make((uint32_t)sh.n);
+    if (sh.k32)
+        pip_keys_hist<uint32_t>(w, sh, scal, fn, s);
+    else
+        pip_keys_hist<uint16_t>(w, sh, scal, fn, s);
+    // the counts in sorted order (transposed), for the start layer
+    k_pip_len0<<<nb_of(nb), PTPB, 0, s>>>(w.len[0], w.len[1], nb, c, (uint32_t)sh.W, w.maxlen, w.S, w.bq);
+    // every step's layout (LEN, PAD, OFF)[t], t = 0 .. steps, and OFF[T] = the sorted-order starts
+    k_pip_lay_part<<<dim3(sh.nparts, T + 1), PTPB, 0, s>>>(w.len[0], w.len[1], T, nb, LEN, PAD, w.part, sh.nparts, TT,
+                                                           w.tailq, w.maxlen + 2);
+    k_pip_lay_fin<<<dim3(sh.nparts, T + 1), PTPB, 0, s>>>(PAD, w.part, sh.nparts, nb, OFF);
+    k_pip_start<<<nb_of(nb), PTPB, 0, s>>>(OFF + (size_t)T * nb, nb, c, (uint32_t)sh.W, w.start);
+    size_t tb = w.temp_bytes;
+    PIP_RET(pip_sort_part(sh, w.temp, tb, w.keys_in, w.keys, w.vals, s));
+    if (sh.k32)
+        k_pip_bidfill<<<nb_of((nb + sh.nbq) * 64), PTPB, 0, s>>>(LEN, OFF, nb, w.maxlen, w.bq, w.bid[0]);
+    else
+        k_pip_bid0<<<nb_of(N), PTPB, 0, s>>>((const uint16_t*)w.keys, w.vals, N, fn, c, w.start, OFF, w.bid[0]);
+    const uint32_t* keys32 = sh.k32 ? (const uint32_t*)w.keys : nullptr;
+    const uint32_t imask = sh.ib >= 32 ? 0xFFFFFFFFu : (uint32_t)((1ull << sh.ib) - 1);
+    // step t: layout t -> t + 1, (bid, data)[t & 1] -> [(t + 1) & 1]
+    // at least nb lanes in every step (step 0 too: when n < 2^c / 4 the padded total is below
+    // 4 nb), so the octet tail path, which takes up to nb / 8 groups, always has its 8 lanes each
+    size_t lanes = std::max((sh.tot0 + 3) / 4, nb);
+    for (int t = 0; t < (TT ? TT + 1 : sh.steps); t++) {
+        const int a = t & 1, b = a ^ 1;
+        const size_t l0 = (size_t)t * nb, l1 = l0 + nb;
+        k_pip_step<<<nb_of(lanes), PTPB, 0, s>>>(t, w.maxlen, P, fn, keys32, imask, w.vals, w.start, w.Q[a], w.bid[a],
+                                                  OFF + l0, LEN + l0, PAD + l0, OFF + l1, w.Q[b], w.bid[b], w.S, nb,
+                                                  lanes, TT ? TT : -1);
+        lanes = lanes / 4 + nb;
+    }
+    if (TT)   // layer TT's lists that need more than one more step (written by step TT - 1 into Q[TT & 1]), in LDS
+        k_pip_tail<<<(unsigned)std::min(nb, (size_t)2048), PTPB, 0, s>>>(w.tailq, w.maxlen + 2, w.Q[TT & 1],
+                                                                         OFF + (size_t)TT * nb, LEN + (size_t)TT * nb,
+                                                                         w.S);
+    return hipGetLastError();
+}
+
+// Chunks -> window sums of part sh into Sw[w0 .. w1-1] of each MSM's Wtot, on stream s (latency-bound).
+static hipError_t pip_finish(const PipWs& w, const PipShape& sh, int Wtot, ge* Sw, const ge* dtab, hipStream_t s) {
+    k_pip_chunks<<<nb_of(8 * sh.W * sh.NC), PTPB, 0, s>>>(w.S, sh.c, (int)sh.W, w.V, dtab);
+    k_pip_window<<<(unsigned)sh.W, PTPB, 0, s>>>(w.V, (int)sh.NC, sh.Wp, Wtot, sh.w0, Sw);
+    return hipGetLastError();
+}
+
+// The pair's side stream and events, made on the pair's first use.  If one cannot be made, those
+// made are destroyed and the pair stays as it was: the next call tries again.
+static hipError_t pip_side(PipPair& pp) {
+    if (pp.side) return hipSuccess;
+    hipStream_t side = nullptr;
+    hipEvent_t ev[3] = {};
+    // a high-priority stream: HIP spreads streams over a few hardware queues, and one that
+    // shared the caller's queue would serialize the chains behind the bottom half again
+    int lo_pr = 0, hi_pr = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&lo_pr, &hi_pr);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, hi_pr);
+    for (auto& v : ev)
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&v, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        for (auto v : ev)
+            if (v) (void)hipEventDestroy(v);
+        if (side) (void)hipStreamDestroy(side);
+        return e;
+    }
+    pp.side = side;
+    std::copy(ev, ev + 3, pp.ev);
+    return hipSuccess;
+}
+
+// The windows run as two parts, top part first, each with its own workspace.  The caller's
+// stream carries the throughput work (sort + bucket trees of both parts, then the bottom part's
+// chunks); the side stream carries the latency-bound chains: the top part's chunks + window trees
+// + its part of the Horner chain (~126 dependent doublings) overlap the bottom part's bucket
+// trees, and only the bottom part's chunks and Horner part remain at the end.  Same values,
+// same bits.
+hipError_t msm_pippenger(PipPair& pp, ge* result, const fe* scal, const ge* P, size_t n, size_t count, int c,
+                         const ge* dtab, hipStream_t s) {
     if (n == 0 || count == 0) return hipSuccess;
-    PipPair* pp = nullptr;
-    PIP_RET(pip_pair(&pp, s));
-    PipWs& hi = pp->hi;
-    PipWs& lo = pp->lo;
+    PIP_RET(pip_side(pp));
 #ifndef BP_PIP_SPLIT8
 #define BP_PIP_SPLIT8 3   // the bottom part's share of the windows, in eighths (3: measured best)
 #endif
     const int W = (256 + c - 1) / c, wm = (W * BP_PIP_SPLIT8) / 8 > 0 ? (W * BP_PIP_SPLIT8) / 8 : 1;
-    PIP_RET(hi.Sw.need(count * W * sizeof(ge)));
-    PIP_RET(hi.Tmid.need(count * sizeof(ge)));
-    ge* Sw = hi.Sw.as<ge>();
-    PIP_RET(pip_buckets(hi, scal, P, n, count, c, wm, W, s));
-    PIP_RET(hipEventRecord(hi.ev[1], s));
-    PIP_RET(hipStreamWaitEvent(hi.side, hi.ev[1], 0));
-    PIP_RET(pip_finish(hi, count, c, W, wm, W, Sw, dtab, hi.side));
-    k_pip_horner<<<(unsigned)count, 64, 0, hi.side>>>(Sw, W, W - 1, wm, c, nullptr, hi.Tmid.as<ge>());
+    const bool f16 = pip_force16();
+    const int tl = pip_tail_layer();
+    const PipShape top = pip_shape(n, count, c, wm, W, f16, tl), bot = pip_shape(n, count, c, 0, wm, f16, tl);
+    PipWs hi, lo;
+    PIP_RET(pip_carve(pp.hi, top, W, s, hi));   // with every window's sum (Sw) and the top part's Horner value (Tmid)
+    PIP_RET(pip_buckets(hi, top, scal, P, s));
+    PIP_RET(hipEventRecord(pp.ev[0], s));
+    PIP_RET(hipStreamWaitEvent(pp.side, pp.ev[0], 0));
+    PIP_RET(pip_finish(hi, top, W, hi.Sw, dtab, pp.side));
+    k_pip_horner<<<(unsigned)count, 64, 0, pp.side>>>(hi.Sw, W, W - 1, wm, c, nullptr, hi.Tmid);
     PIP_RET(hipGetLastError());
-    PIP_RET(pip_buckets(lo, scal, P, n, count, c, 0, wm, s));
-    PIP_RET(pip_finish(lo, count, c, W, 0, wm, Sw, dtab, s));
-    PIP_RET(hipEventRecord(hi.ev[2], s));
-    PIP_RET(hipStreamWaitEvent(hi.side, hi.ev[2], 0));
-    k_pip_horner<<<(unsigned)count, 64, 0, hi.side>>>(Sw, W, wm - 1, 0, c, hi.Tmid.as<ge>(), result);
+    PIP_RET(pip_carve(pp.lo, bot, 0, s, lo));
+    PIP_RET(pip_buckets(lo, bot, scal, P, s));
+    PIP_RET(pip_finish(lo, bot, W, hi.Sw, dtab, s));
+    PIP_RET(hipEventRecord(pp.ev[1], s));
+    PIP_RET(hipStreamWaitEvent(pp.side, pp.ev[1], 0));
+    k_pip_horner<<<(unsigned)count, 64, 0, pp.side>>>(hi.Sw, W, wm - 1, 0, c, hi.Tmid, result);
     PIP_RET(hipGetLastError());
-    PIP_RET(hipEventRecord(hi.ev[3], hi.side));
-    PIP_RET(hipStreamWaitEvent(s, hi.ev[3], 0));          // the result is ready in the caller's stream order
+    PIP_RET(hipEventRecord(pp.ev[2], pp.side));
+    PIP_RET(hipStreamWaitEvent(s, pp.ev[2], 0));          // the result is ready in the caller's stream order
     return hipSuccess;
 }
 
 // Window sums of windows [w0, w1) of one MSM into Sw[w0 .. w1) (entries outside untouched), all on
-// stream s: the same keys, sort, bucket trees, chunks and window trees as msm_pippenger's parts,
-// so each S_w has the bits the single call forms.  A multi-GPU MSM gives each rank a window range
-// and exchanges the 128-byte sums (cudabulletproof_amd/shard.py sharded_msm_pippenger).
-hipError_t msm_pippenger_windows(ge* Sw, const fe* scal, const ge* P, size_t n, int c, int w0, int w1,
+// stream s, in the pair's bottom workspace: the same keys, sort, bucket trees, chunks and window
+// trees as msm_pippenger's parts, so each S_w has the bits the single call forms.  A multi-GPU MSM
+// gives each rank a window range and exchanges the 128-byte sums (cudabulletproof_amd/shard.py
+// sharded_msm_pippenger).
+hipError_t msm_pippenger_windows(PipPair& pp, ge* Sw, const fe* scal, const ge* P, size_t n, int c, int w0, int w1,
                                  const ge* dtab, hipStream_t s) {
     const int W = (256 + c - 1) / c;
     if (n == 0 || w0 >= w1 || w0 < 0 || w1 > W) return hipSuccess;
-    PipPair* pp = nullptr;
-    PIP_RET(pip_pair(&pp, s));
-    PIP_RET(pip_buckets(pp->lo, scal, P, n, 1, c, w0, w1, s));
-    return pip_finish(pp->lo, 1, c, W, w0, w1, Sw, dtab, s);
-}
-
-// Frees stream s's workspace pair on the current device (hipbp_release_stream_workspaces): waits
-// for s and the pair's side stream, frees every buffer, destroys the side stream and events.
-hipError_t pippenger_release(hipStream_t s) {
-    int dev = 0;
-    PIP_RET(hipGetDevice(&dev));
-    PipPair* pp = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_pip_mu);
-        auto it = g_pip.find(std::make_pair(dev, s));
-        if (it == g_pip.end()) return hipSuccess;
-        pp = it->second;
-        g_pip.erase(it);
-    }
-    // keep freeing after an error (the pair is already out of the map): the first error is returned
-    hipError_t first = hipStreamSynchronize(s);
-    auto keep = [&first](hipError_t r) { if (first == hipSuccess) first = r; };
-    if (pp->hi.side) keep(hipStreamSynchronize(pp->hi.side));
-    for (PipWs* w : {&pp->hi, &pp->lo}) {
-        for (DBuf* b : {&w->keys_in, &w->keys, &w->vals, &w->temp, &w->start, &w->len[0], &w->len[1], &w->lay,
-                        &w->bq, &w->bid[0], &w->bid[1], &w->Q[0], &w->Q[1], &w->S, &w->V, &w->Sw, &w->Tmid,
-                        &w->maxlen, &w->part, &w->tailq})
-            if (b->p) {
-                keep(hipFree(b->p));
-                b->p = nullptr;
-            }
-        for (auto& ev : w->ev)
-            if (ev) {
-                keep(hipEventDestroy(ev));
-                ev = nullptr;
-            }
-        if (w->side) {
-            keep(hipStreamDestroy(w->side));
-            w->side = nullptr;
-        }
-    }
-    delete pp;
-    return first;
+    PIP_RET(pip_side(pp));
+    const PipShape sh = pip_shape(n, 1, c, w0, w1, pip_force16(), pip_tail_layer());
+    PipWs lo;
+    PIP_RET(pip_carve(pp.lo, sh, 0, s, lo));
+    PIP_RET(pip_buckets(lo, sh, scal, P, s));
+    return pip_finish(lo, sh, W, Sw, dtab, s);
 }
 
 // Horner over all W window sums of `count` MSMs (Sw[m W .. m W + W)), on stream s.

@@ -8,6 +8,7 @@
 //   pack:      proofs with distinct bytes in every field, packed and read back through the batch view
 //   unpack:    a pattern written through the hipbp_proof_out view, unpacked into RangeProof structs
 //   tables:    every workspace buffer's bytes
+//   pippenger: the Pippenger part's shape and buffer bytes over a grid of shapes
 // Prints "<checks> <failures>"; exit status 1 on any failure.
 #include <cstdio>
 #include <cstdlib>
@@ -315,11 +316,92 @@ static void tables() {
     }
 }
 
+// The Pippenger part: every shape field and every buffer's bytes against the expressions
+// bp_pippenger.hip computed in line before it had a table (256 threads per block, 16 buckets per
+// chunk, 4 x 256 buckets per scan block, 4096 list elements per bidfill piece), over
+// n x c x count x {all windows, the first, the top part [wm, W)} x key width x tail layer.
+static void pippenger() {
+    using namespace bp;
+    const size_t ns[] = {1, 3, 4, 63, 64, 1000, 3000, 65536, (size_t)1 << 20}, counts[] = {1, 3};
+    const int cs[] = {4, 8, 12}, tls[] = {1, 4, 8};
+    bool seen_k32[2] = {}, seen_TT[2] = {}, seen_odd = false, seen_sparse = false, seen_nbq1 = false;
+    for (size_t n : ns)
+        for (int c : cs)
+            for (size_t count : counts)
+                for (int range = 0; range < 3; range++)
+                    for (int force16 = 0; force16 < 2; force16++)
+                        for (int tl : tls) {
+                            const int Wt = (256 + c - 1) / c, wm = (Wt * 3) / 8 > 0 ? (Wt * 3) / 8 : 1;
+                            const int w0 = range == 2 ? wm : 0, w1 = range == 1 ? 1 : Wt;
+                            const size_t Wtot = range == 2 ? Wt : 0, temp = 1000 + n;   // (any byte count)
+                            // the old expressions
+                            const int Wp = w1 - w0;
+                            const size_t W = (size_t)Wp * count;
+                            const size_t NB = (size_t)1 << c, nb = W * NB, N = W * n, NC = NB / 16;
+                            int ib = 0;
+                            while (ib < 32 && ((size_t)1 << ib) < n) ib++;
+                            const bool k32 = c + ib <= 32 && !force16;
+                            int levels = 1;
+                            while (levels < 31 && ((size_t)1 << levels) < n) levels++;
+                            const int steps = (levels + 1) / 2, T = steps + 1;
+                            const unsigned nparts = (unsigned)((nb + 1024 - 1) / 1024);
+                            const size_t tot0 = N + 3 * nb, qcap = tot0 / 4 + 4 * nb;
+                            const int TT = steps > tl ? tl : 0;
+                            const size_t nbq = N / 4096 + 1;
+
+                            const PipShape s = pip_shape(n, count, c, w0, w1, force16 != 0, tl);
+                            CHECK(s.n == n && s.count == count && s.c == c && s.w0 == w0, "pip shape inputs");
+                            CHECK(s.Wp == Wp, "pip Wp");
+                            CHECK(s.W == W, "pip W");
+                            CHECK(s.NB == NB, "pip NB");
+                            CHECK(s.nb == nb, "pip nb");
+                            CHECK(s.N == N, "pip N");
+                            CHECK(s.NC == NC, "pip NC");
+                            CHECK(s.ib == ib, "pip ib n=%zu", n);
+                            CHECK(s.k32 == k32, "pip k32");
+                            CHECK(s.levels == levels, "pip levels n=%zu", n);
+                            CHECK(s.steps == steps, "pip steps");
+                            CHECK(s.T == T, "pip T");
+                            CHECK(s.nparts == nparts, "pip nparts");
+                            CHECK(s.tot0 == tot0, "pip tot0");
+                            CHECK(s.qcap == qcap, "pip qcap");
+                            CHECK(s.nbq == nbq, "pip nbq");
+                            CHECK(s.TT == TT, "pip TT");
+                            size_t sz[PIP_COUNT];
+                            pip_sizes(s, Wtot, temp, sz);
+                            const size_t kb = N * (k32 ? 4 : 2);
+                            CHECK(sz[PIP_KEYS_IN] == kb && sz[PIP_KEYS] == kb && sz[PIP_VALS] == (k32 ? 0 : N * 4) &&
+                                  sz[PIP_START] == nb * 4 && sz[PIP_LEN0] == nb * 4 && sz[PIP_LEN1] == nb * 4 &&
+                                  sz[PIP_LAY] == (size_t)3 * (T + 1) * nb * 4 && sz[PIP_PART] == (size_t)(T + 1) * nparts * 4 &&
+                                  sz[PIP_BID0] == tot0 * 4 && sz[PIP_BID1] == qcap * 4 && sz[PIP_Q0] == qcap * 128 &&
+                                  sz[PIP_Q1] == qcap * 128 && sz[PIP_V] == W * NC * 128 && sz[PIP_S] == nb * 128 &&
+                                  sz[PIP_MAXLEN] == 12 && sz[PIP_TAILQ] == (TT ? nb * 4 : 0) && sz[PIP_BQ] == nbq * 8 &&
+                                  sz[PIP_SW] == count * Wtot * 128 && sz[PIP_TMID] == (Wtot ? count * 128 : 0) &&
+                                  sz[PIP_TEMP] == temp, "pip buffers by name n=%zu c=%d", n, c);
+                            const size_t sum = 2 * kb + (k32 ? 0 : N * 4) + 3 * nb * 4 + 3 * (T + 1) * nb * 4 +
+                                               (T + 1) * nparts * 4 + (tot0 + qcap) * 4 + (2 * qcap + W * NC + nb) * 128 + 12 +
+                                               (TT ? nb * 4 : 0) + nbq * 8 + (Wtot ? count * (Wtot + 1) * 128 : 0) + temp;
+                            check_table("pip", sz,
+                                        {kb, kb, k32 ? 0 : N * 4, nb * 4, nb * 4, nb * 4, (size_t)3 * (T + 1) * nb * 4,
+                                         (size_t)(T + 1) * nparts * 4, tot0 * 4, qcap * 4, qcap * 128, qcap * 128, W * NC * 128,
+                                         nb * 128, 12, TT ? nb * 4 : 0, nbq * 8, count * Wtot * 128, Wtot ? count * 128 : 0,
+                                         temp}, sum);
+                            seen_k32[k32] = seen_TT[TT > 0] = true;
+                            seen_odd |= n % 4 != 0;
+                            seen_sparse |= n < NB / 4;
+                            seen_nbq1 |= N / 4096 == 0;
+                        }
+    CHECK(seen_k32[0] && seen_k32[1], "pip grid: both key widths");
+    CHECK(seen_TT[0] && seen_TT[1], "pip grid: with and without the LDS tail");
+    CHECK(seen_odd && seen_sparse && seen_nbq1, "pip grid: n %% 4 != 0, n < 2^c / 4, N / BID_PIECE == 0");
+}
+
 int main() {
     offsets();
     pack_view();
     unpack();
     tables();
+    pippenger();
     std::printf("%llu %llu\n", checks, fails);
     return fails ? 1 : 0;
 }

@@ -1170,6 +1170,50 @@ def test_msm_pippenger_sparse_buckets_all_apis(bp, oracle, n, c):
     assert np.array_equal(Sw.cpu().numpy().view(np.uint64), oracle.pippenger_windows(s[:n], P, c, 0, W))
 
 
+def test_msm_pippenger_workspace_growth(bp, oracle):
+    """One stream's Pippenger pair grown while live, then reused: a small MSM, a batch that needs every
+    buffer larger (the first call's buffers are freed to grow), the small MSM again in the larger
+    buffers, and a window split + Horner (the bottom workspace alone) — no release in between, each
+    result the oracle's bits.  Then the stream's workspaces are released and the first MSM rebuilds them."""
+    import torch
+    dev = torch.device("cuda:0")
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).to(dev)
+    rng = np.random.default_rng(4242)
+    n0, c0, n1, c1, count = 64, 4, 1500, 8, 3
+    P0, P1 = oracle.base_points(n0, 51), oracle.base_points(n1, 52)
+    s0, s1 = rand_fe(rng, n0), rand_fe(rng, count * n1)
+    s1[::9] = s1[0]   # a crowded bucket per window
+    want0 = oracle.msm_pippenger(s0, P0, c0)
+    want1 = [oracle.msm_pippenger(s1[m * n1:(m + 1) * n1], P1, c1) for m in range(count)]
+    W = (256 + c1 - 1) // c1
+    want_sw = oracle.pippenger_windows(s1[:n1], P1, c1, 0, W)
+    s0d, P0d, s1d, P1d = T(s0), T(P0), T(s1), T(P1)
+    small = torch.zeros(3, 16, dtype=torch.int64, device=dev)
+    big = torch.zeros(count, 16, dtype=torch.int64, device=dev)
+    Sw = torch.zeros(W, 16, dtype=torch.int64, device=dev)
+    wo = torch.zeros(1, 16, dtype=torch.int64, device=dev)
+    st = torch.cuda.Stream(dev)
+    torch.cuda.synchronize()   # the inputs and the zero fills are on torch's stream, the MSMs are not
+    bp.msm_pippenger(small[0], s0d, P0d, c0, stream=st)
+    bp.msm_pippenger_batch(big, s1d, P1d, c1, stream=st)
+    bp.msm_pippenger(small[1], s0d, P0d, c0, stream=st)
+    bp.msm_pippenger_windows(Sw, s1d[:n1], P1d, 0, 5, c1, stream=st)
+    bp.msm_pippenger_windows(Sw, s1d[:n1], P1d, 5, W, c1, stream=st)
+    bp.msm_pippenger_horner(wo, Sw, c1, stream=st)
+    bp.release_stream_workspaces(st)   # waits for st first
+    bp.msm_pippenger(small[2], s0d, P0d, c0, stream=st)
+    torch.cuda.synchronize()
+    got = small.cpu().numpy().view(np.uint64)
+    for k in range(3):
+        assert np.array_equal(got[k], want0), k
+    got = big.cpu().numpy().view(np.uint64)
+    for m in range(count):
+        assert np.array_equal(got[m], want1[m]), m
+    assert np.array_equal(Sw.cpu().numpy().view(np.uint64), want_sw)
+    assert np.array_equal(wo.cpu().numpy().view(np.uint64)[0], want1[0])
+    bp.release_stream_workspaces(st)
+
+
 # ----------------------------------------------------------------------------- batched MSM
 @pytest.mark.parametrize("n,count", [(1, 3), (17, 5), (300, 4), (256, 2)])
 def test_msm_batch_matches_single(bp, oracle, n, count):

@@ -8,6 +8,11 @@ stand-alone host program:
 * pack / view and output / unpack round trips with distinct bytes in every field, with and without
   the range-proof part, with refused proofs, at L_len = 0 and with a short last chunk.
 * every buffer of the prover, IPA, MSM and verify-slot tables has its listed size.
+* the Pippenger part: over n in {1, 3, 4, 63, 64, 1000, 3000, 65536, 2^20}, c in {4, 8, 12}, count in
+  {1, 3}, the window ranges [0, W), [0, 1), [wm, W), both key widths and tail layers {1, 4, 8}, every
+  field of pip_shape and every buffer's bytes equal the expressions bp_pippenger.hip computed in line
+  before it had a table; the grid reaches both key widths, a part with and without the LDS tail,
+  n % 4 != 0, n < 2^c / 4 and a bidfill queue of one entry.
 
 Once at -O2 and once under AddressSanitizer + UndefinedBehaviourSanitizer (host code only, nothing
 loaded into Python): the round trips use exactly sized buffers and free every vector handed out."""
@@ -34,7 +39,8 @@ def _run(exe):
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     checks, fails = (int(x) for x in r.stdout.split("\n")[-2].split())
     # 48 chunk shapes and 96 output shapes of >= 12 regions, 72 round trips, 12 unpack shapes, the tables
-    assert fails == 0 and checks >= 5000, r.stdout[-3000:]
+    # (5000 at least), and 40 checks for each of the Pippenger grid's 972 shapes + 3 for its coverage
+    assert fails == 0 and checks >= 5000 + 972 * 40 + 3, r.stdout[-3000:]
     return r
 
 
