@@ -128,6 +128,8 @@ EXPORTS = [
     "hipbp_batch_inner_product_prove", "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host",
     "hipbp_derive_prover_scalars", "hipbp_batch_generate_range_proof_seeded",
     "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host",
+    "hipbp_batch_generate_range_proof_accepted", "hipbp_batch_generate_range_proof_accepted_gens",
+    "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats",
 ]
 
 
@@ -157,7 +159,9 @@ def lib():
                   "hipbp_release_stream_workspaces", "hipbp_batch_inner_product_prove",
                   "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host",
                   "hipbp_derive_prover_scalars", "hipbp_batch_generate_range_proof_seeded",
-                  "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host"):
+                  "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host",
+                  "hipbp_batch_generate_range_proof_accepted", "hipbp_batch_generate_range_proof_accepted_gens",
+                  "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats"):
             getattr(L, f).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -549,6 +553,82 @@ def batch_generate_range_proof_seeded(n, v, gamma, seed, G, H, g, h, index_base=
                                                            _stream_ptr(stream)))
     out["_keep"] = ins
     return out
+
+
+# ---------------------------------------------------------------------- accepted prover
+def derive_prover_scalars_at(n, v, gamma, seed, attempt=None, index_base=0, stream=None):
+    """hipbp_derive_prover_scalars_at: derive_prover_scalars for chosen attempts.
+
+    attempt: (B,) uint8 CUDA tensor, proof p's 0-based attempt index (its scalars come from the try
+    key key_{p, attempt[p]}); None: every proof's attempt 0, derive_prover_scalars itself.  With
+    attempt = max(attempts, 1) - 1 of a batch_generate_range_proof_accepted result these are the
+    scalars its proofs were proved with.  Returns derive_prover_scalars' dict."""
+    import contextlib
+
+    import torch
+    sd = _seed_arg(seed)
+    B, n = int(v.shape[0]), int(n)
+    ins = [v.contiguous(), gamma.contiguous()]
+    if attempt is not None:
+        if attempt.dtype != torch.uint8 or tuple(attempt.shape) != (B,):
+            raise ValueError(f"attempt must be a ({B},) uint8 tensor")
+        ins.append(attempt.contiguous())
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=v.device)
+        out = dict(sL=z(B, n, 4), sR=z(B, n, 4), rnd=z(B, 4, 4))
+    _chk(lib().hipbp_derive_prover_scalars_at(sd, _c(ins[0].data_ptr()), _c(ins[1].data_ptr()),
+                                              ctypes.c_uint64(int(index_base) & (2**64 - 1)),
+                                              _c(ins[2].data_ptr()) if attempt is not None else None, _sz(B), _sz(n),
+                                              _c(out["sL"].data_ptr()), _c(out["sR"].data_ptr()),
+                                              _c(out["rnd"].data_ptr()), _stream_ptr(stream)))
+    out["_keep"] = ins
+    return out
+
+
+def batch_generate_range_proof_accepted(n, v, gamma, seed, G, H, g, h, index_base=0, max_attempts=8, check=1,
+                                        stream=None, gens=None):
+    """batch_generate_range_proof_seeded whose proofs the library's own verifier accepts
+    (hipbp_batch_generate_range_proof_accepted): the seeded proofs are verified on the
+    GPU (check 1: batch_range_proof_verify's semantics, check 2: batch_range_proof_verify_std's) and
+    each rejected one is proved again, up to max_attempts (1..16) attempts in all, with the scalars
+    of its next try key.  SYNCHRONOUS: the outputs are complete on return.
+
+    Returns the prover's dict plus "attempts" (B,) uint8: k >= 1, accepted at the k-th attempt (the
+    proof of derive_prover_scalars_at(attempt = k - 1)); 0, refused (valid 0) or not accepted
+    within max_attempts (valid 1; the last attempt's proof)."""
+    import contextlib
+
+    import torch
+    sd = _seed_arg(seed)
+    B = int(v.shape[0])
+    out, oc = _proof_out(B, n, v.device, stream)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        out["attempts"] = torch.empty(B, dtype=torch.uint8, device=v.device)
+    ins = [v.contiguous(), gamma.contiguous()]
+    ic = ProveInputC(B, int(n), ins[0].data_ptr(), ins[1].data_ptr(), None, None, None)
+    ib = ctypes.c_uint64(int(index_base) & (2**64 - 1))
+    tail = (ctypes.byref(oc), _c(out["attempts"].data_ptr()), _stream_ptr(stream))
+    if gens is not None:   # the set's generators and prefix tables (G, H, g, h are not read)
+        _chk(lib().hipbp_batch_generate_range_proof_accepted_gens(ctypes.byref(ic), sd, ib, ctypes.c_int(max_attempts),
+                                                                  ctypes.c_int(check), _c(gens.h), *tail))
+    else:
+        _chk(lib().hipbp_batch_generate_range_proof_accepted(ctypes.byref(ic), sd, ib, ctypes.c_int(max_attempts),
+                                                             ctypes.c_int(check), _c(G.data_ptr()), _c(H.data_ptr()),
+                                                             _c(g.data_ptr()), _c(h.data_ptr()), *tail))
+    out["_keep"] = ins
+    return out
+
+
+def accepted_last_stats():
+    """hipbp_accepted_last_stats: the calling thread's last accepted call as dict(rounds, proved (the
+    proofs proved in each round), kernel_ms (try_keys, select, scatter; zeros unless
+    HIPBP_ACCEPT_TIMING=1 was set when the call ran))."""
+    r = ctypes.c_int(0)
+    m = (ctypes.c_uint32 * 16)()
+    ms = (ctypes.c_float * 3)()
+    _chk(lib().hipbp_accepted_last_stats(ctypes.byref(r), m, ms))
+    return dict(rounds=r.value, proved=list(m)[:r.value],
+                kernel_ms=dict(zip(("try_keys", "select", "scatter"), (float(x) for x in ms))))
 
 
 def _take(vec, words):

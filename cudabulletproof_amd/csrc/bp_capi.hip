@@ -117,6 +117,10 @@ struct StreamWs {
     // seeded prover (hipbp_batch_generate_range_proof_seeded): the per-proof keys and the derived
     // scalars of a batch, rnd | sL | sR
     Buf seed_keys, seed_scal;
+    // accepted prover (hipbp_batch_generate_range_proof_accepted): the retry loop's buffers and the
+    // pinned word its rejected count is read back into; guarded by seed_mu, held for the whole call
+    Buf accept[bp::AB_COUNT];
+    PinnedBuf accept_cnt;
     // stand-alone IPA prover (hipbp_batch_inner_product_prove): two chunk workspaces, the second run
     // on an internal side stream so one chunk's latency-bound chains run under the other's scalar
     // multiplications (the Pippenger path's scheme)
@@ -174,7 +178,8 @@ struct Engine {
     std::mutex prove_host_mu;
     // the per-stream workspaces (guarded by mu).  seed_mu is held from the seeded prover's derive
     // launches to the end of the prover's enqueue (taken before `mu`), so two host threads on one
-    // stream cannot interleave a derivation between another's derivation and its prover.
+    // stream cannot interleave a derivation between another's derivation and its prover; the
+    // accepted prover, whose retry rounds read the batch's keys again, holds it for its whole call.
     std::map<hipStream_t, StreamWs> streams;
     std::mutex seed_mu;
     std::mutex mu;
@@ -559,6 +564,8 @@ hipError_t StreamWs::release(hipError_t first) {
     for (auto& b : prove) keep(b.release());
     keep(seed_keys.release());
     keep(seed_scal.release());
+    for (auto& b : accept) keep(b.release());
+    keep(accept_cnt.release());
     if (ipa_side) keep(hipStreamSynchronize(ipa_side));
     for (auto& half : ipa)
         for (auto& b : half) keep(b.release());
@@ -1038,6 +1045,7 @@ int hipbp_derive_prover_scalars(const uint8_t* seed32, const fe25519* v, const f
     if (!sL || !sR || !rnd) { g_err = "derive: null output"; return HIPBP_ERR_ARG; }
     if (count == 0) return HIPBP_OK;
     hipStream_t s = pick(stream);
+    std::lock_guard<std::mutex> slk(e->seed_mu);   // (the stream's keys: an accepted call may still need its own)
     std::lock_guard<std::mutex> lk(e->mu);
     StreamWs* sb = nullptr;
     if ((rc = seed_keys(*e, s, count, &sb)) != HIPBP_OK) return rc;
@@ -1047,21 +1055,50 @@ int hipbp_derive_prover_scalars(const uint8_t* seed32, const fe25519* v, const f
     return HIPBP_OK;
 }
 
-static int prove_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base, const ge25519* G,
-                        const ge25519* H, const ge25519* g, const ge25519* h, const bp::ge* ptab, int pbits,
-                        hipbp_proof_out* out, void* stream) {
+// The derivation of chosen attempts: proof p's scalars under key_{p, attempt[p]}.  The
+// try keys go through the accepted prover's key buffer, so this call takes seed_mu as that one does.
+int hipbp_derive_prover_scalars_at(const uint8_t* seed32, const fe25519* v, const fe25519* gamma, uint64_t index_base,
+                                   const uint8_t* attempt, size_t count, size_t n, fe25519* sL, fe25519* sR,
+                                   fe25519* rnd, void* stream) {
+    if (!attempt) return hipbp_derive_prover_scalars(seed32, v, gamma, index_base, count, n, sL, sR, rnd, stream);
     BP_ENGINE_OR_RET(e);
+    int rc = seed_check(seed32, v, gamma, count, n);
+    if (rc != HIPBP_OK) return rc;
+    if (!sL || !sR || !rnd) { g_err = "derive: null output"; return HIPBP_ERR_ARG; }
+    if (count == 0) return HIPBP_OK;
+    hipStream_t s = pick(stream);
+    std::lock_guard<std::mutex> slk(e->seed_mu);
+    std::lock_guard<std::mutex> lk(e->mu);
+    StreamWs* sb = nullptr;
+    if ((rc = seed_keys(*e, s, count, &sb)) != HIPBP_OK) return rc;
+    BP_RET_ON(sb->accept[bp::AB_KEYS].need(count * sizeof(bp::fe)));
+    bp::fe *keys = sb->seed_keys.as<bp::fe>(), *tkeys = sb->accept[bp::AB_KEYS].as<bp::fe>();
+    bp::launch_seed_keys(bp::seed_words(seed32), (const bp::fe*)v, (const bp::fe*)gamma, index_base, (uint32_t)count,
+                         (uint32_t)n, keys, s);
+    bp::launch_try_keys_at(keys, attempt, (uint32_t)count, tkeys, s);
+    bp::launch_seed_scalars(tkeys, (uint32_t)count, (uint32_t)n, (bp::fe*)sL, (bp::fe*)sR, (bp::fe*)rnd, s);
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+// what the seeded and the accepted prover check of their arguments before anything is enqueued
+static int prove_seeded_check(const hipbp_prove_input* in, const uint8_t* seed32, const ge25519* G, const ge25519* H,
+                              const ge25519* g, const ge25519* h, const hipbp_proof_out* out) {
     if (!in || !out || !G || !H || !g || !h) { g_err = "null argument"; return HIPBP_ERR_ARG; }
     if (in->sL || in->sR || in->rnd) {
         g_err = "seeded prover: sL, sR and rnd must be NULL (the scalars are derived from the seed)";
         return HIPBP_ERR_ARG;
     }
-    int rc = seed_check(seed32, in->v, in->gamma, in->count, in->n);
-    if (rc != HIPBP_OK) return rc;
-    if (in->count == 0) return HIPBP_OK;
+    return seed_check(seed32, in->v, in->gamma, in->count, in->n);
+}
+
+// the seeded prover's derive launches and prover enqueue: arguments checked, count > 0, seed_mu held
+static int prove_seeded_locked(Engine* e, const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base,
+                               const ge25519* G, const ge25519* H, const ge25519* g, const ge25519* h,
+                               const bp::ge* ptab, int pbits, hipbp_proof_out* out, void* stream) {
+    int rc;
     const size_t B = in->count, n = in->n;
     hipStream_t s = pick(stream);
-    std::lock_guard<std::mutex> slk(e->seed_mu);
     bp::fe* scal = nullptr;
     {
         std::lock_guard<std::mutex> lk(e->mu);
@@ -1081,6 +1118,17 @@ static int prove_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint
     return prove_run(&full, G, H, g, h, ptab, pbits, out, stream);
 }
 
+static int prove_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base, const ge25519* G,
+                        const ge25519* H, const ge25519* g, const ge25519* h, const bp::ge* ptab, int pbits,
+                        hipbp_proof_out* out, void* stream) {
+    BP_ENGINE_OR_RET(e);
+    int rc = prove_seeded_check(in, seed32, G, H, g, h, out);
+    if (rc != HIPBP_OK) return rc;
+    if (in->count == 0) return HIPBP_OK;
+    std::lock_guard<std::mutex> slk(e->seed_mu);
+    return prove_seeded_locked(e, in, seed32, index_base, G, H, g, h, ptab, pbits, out, stream);
+}
+
 int hipbp_batch_generate_range_proof_seeded(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base,
                                             const ge25519* G, const ge25519* H, const ge25519* g, const ge25519* h,
                                             hipbp_proof_out* out, void* stream) {
@@ -1094,6 +1142,168 @@ int hipbp_batch_generate_range_proof_seeded_gens(const hipbp_prove_input* in, co
     return prove_seeded(in, seed32, index_base, (const ge25519*)gs->G(), (const ge25519*)gs->H(),
                         (const ge25519*)gs->g(), (const ge25519*)gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr,
                         gs->bits, out, stream);
+}
+
+// ---- accepted prover: the seeded prover, the one-shot verify of its proofs, and up to
+// max_attempts - 1 retry rounds over the proofs the verifier rejected, each with the scalars of
+// the next try key.  What the last call on this thread did, for tools/bench_prove_accepted.py:
+// the proofs proved per round and, with HIPBP_ACCEPT_TIMING=1, the loop's own kernels' times.
+enum { AK_TRY_KEYS, AK_SELECT, AK_SCATTER, AK_COUNT };
+struct AcceptStats {
+    int rounds = 0;
+    uint32_t m[16] = {};
+    float ms[AK_COUNT] = {};
+};
+static thread_local AcceptStats g_accept_stats;
+
+// HIP events round the loop's own launches, read after the call's last synchronise
+struct AcceptClock {
+    struct Rec { int kind; hipEvent_t a, b; };
+    const bool on;
+    hipStream_t s;
+    std::vector<Rec> recs;
+    AcceptClock(hipStream_t st) : on(getenv("HIPBP_ACCEPT_TIMING") && atoi(getenv("HIPBP_ACCEPT_TIMING")) != 0), s(st) {}
+    void begin(int kind) {
+        if (!on) return;
+        Rec r{kind, nullptr, nullptr};
+        if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) return;
+        (void)hipEventRecord(r.a, s);
+        recs.push_back(r);
+    }
+    void end() {
+        if (on && !recs.empty()) (void)hipEventRecord(recs.back().b, s);
+    }
+    void collect(float (&ms)[AK_COUNT]) {
+        for (auto& r : recs) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ms[r.kind] += t;
+        }
+    }
+    ~AcceptClock() {
+        for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+    }
+};
+
+static bp::ProveOut prove_out_of(const hipbp_proof_out& o) {
+    return bp::ProveOut{(bp::ge*)o.V, (bp::ge*)o.A, (bp::ge*)o.S, (bp::ge*)o.T1, (bp::ge*)o.T2,
+                        (bp::fe*)o.taux, (bp::fe*)o.mu, (bp::fe*)o.t, (bp::fe*)o.c, (bp::fe*)o.x,
+                        (bp::fe*)o.a, (bp::fe*)o.b, (bp::ge*)o.L, (bp::ge*)o.R, o.valid};
+}
+
+// vtab, vbits: a generator set's prefix tables for the verify (check 1: the one-shot verify takes
+// them there, hipbp_batch_range_proof_verify_gens); ptab, pbits: for the prover.
+static int prove_accepted(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base, int max_attempts,
+                          int check, const ge25519* G, const ge25519* H, const ge25519* g, const ge25519* h,
+                          const bp::ge* ptab, int pbits, hipbp_proof_out* out, uint8_t* attempts, void* stream) {
+    using namespace bp;   // the table's ids and types
+    BP_ENGINE_OR_RET(e);
+    int rc = prove_seeded_check(in, seed32, G, H, g, h, out);
+    if (rc != HIPBP_OK) return rc;
+    if (max_attempts < 1 || max_attempts > 16) { g_err = "accepted prover: max_attempts must be 1..16"; return HIPBP_ERR_ARG; }
+    if (check != 1 && check != 2) { g_err = "accepted prover: check must be 1 or 2"; return HIPBP_ERR_ARG; }
+    g_accept_stats = AcceptStats{};
+    if (in->count == 0) return HIPBP_OK;   // nothing read or written: empty outputs may be null
+    if (!attempts) { g_err = "accepted prover: null attempts"; return HIPBP_ERR_ARG; }
+    const size_t B = in->count, n = in->n, Lr = (size_t)log2i(n);
+    hipStream_t s = pick(stream);
+    AcceptClock clk(s);
+    std::lock_guard<std::mutex> slk(e->seed_mu);
+    // round 1: the seeded prover's proofs (attempt 0) into the caller's output
+    if ((rc = prove_seeded_locked(e, in, seed32, index_base, G, H, g, h, ptab, pbits, out, stream)) != HIPBP_OK) return rc;
+    hipbp_proof_out cur = *out;      // the round's proofs: the caller's output, then the compact workspace
+    const uint32_t* src = nullptr;   // their batch indices (null: the whole batch)
+    size_t m = B;
+    StreamWs* sb = nullptr;
+    AcceptWs w{};
+    size_t sz[AB_COUNT];
+    for (int round = 1;; round++) {
+        g_accept_stats.m[round - 1] = (uint32_t)m;
+        g_accept_stats.rounds = round;
+        {
+            std::lock_guard<std::mutex> lk(e->mu);
+            sb = &e->streams[s];
+            Buf(&b)[AB_COUNT] = sb->accept;
+            accept_sizes(m, 0, n, Lr, sz);
+            BP_RET_ON(need_all(b, sz));
+            BP_RET_ON(sb->accept_cnt.need(sizeof(uint32_t)));
+            BP_ACCEPT_BUFS(BP_BUF_FIELD)
+            hipbp_proof_batch bv{};
+            bv.count = m; bv.n = n; bv.ab_len = 1; bv.L_len = Lr;
+            bv.V = cur.V; bv.A = cur.A; bv.S = cur.S; bv.T1 = cur.T1; bv.T2 = cur.T2;
+            bv.t = cur.t; bv.a = cur.a; bv.b = cur.b; bv.c = cur.c; bv.x = cur.x; bv.L = cur.L; bv.R = cur.R;
+            bv.taux = cur.taux; bv.mu = cur.mu;
+            const bool tabs = check == 1 && ptab;
+            if ((rc = run_verify(*e, &bv, nullptr, G, H, h, w.ok, nullptr, nullptr, check, s, check == 2 ? g : nullptr,
+                                 nullptr, nullptr, tabs ? ptab : nullptr, tabs ? pbits : 0)) != HIPBP_OK)
+                return rc;
+            clk.begin(AK_SELECT);
+            launch_accept_count(w.ok, cur.valid, src, (uint32_t)m, (uint32_t)round, attempts, w.blk, w.cnt, s);
+            clk.end();
+            if (src) {   // a retry round's proofs, accepted or not, to their rows of the caller's output
+                clk.begin(AK_SCATTER);
+                launch_accept_scatter(prove_out_of(cur), prove_out_of(*out), src, (uint32_t)m, (uint32_t)Lr, s);
+                clk.end();
+            }
+            BP_RET_ON(hipGetLastError());
+            if (round < max_attempts)
+                BP_RET_ON(hipMemcpyAsync(sb->accept_cnt.p, w.cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
+        BP_RET_ON(hipStreamSynchronize(s));
+        if (round == max_attempts) break;
+        const size_t r = *sb->accept_cnt.as<uint32_t>();
+        if (r == 0) break;
+        if (r > m) { g_err = "accepted prover: rejected count exceeds the round (internal)"; return HIPBP_ERR_DEVICE; }
+        {
+            std::lock_guard<std::mutex> lk(e->mu);
+            Buf(&b)[AB_COUNT] = sb->accept;
+            accept_sizes(0, r, n, Lr, sz);
+            BP_RET_ON(need_all(b, sz));
+            BP_ACCEPT_BUFS(BP_BUF_FIELD)
+            uint32_t* list = w.list[round & 1];
+            clk.begin(AK_SELECT);
+            launch_accept_fill(w.ok, cur.valid, src, (uint32_t)m, w.blk, (const fe*)in->v, (const fe*)in->gamma, list, w.v,
+                               w.gamma, s);
+            clk.end();
+            clk.begin(AK_TRY_KEYS);
+            launch_try_keys_list(sb->seed_keys.as<fe>(), list, (uint32_t)r, (uint32_t)round, w.keys, s);
+            clk.end();
+            launch_seed_scalars(w.keys, (uint32_t)r, (uint32_t)n, w.scal + 4 * r, w.scal + (4 + n) * r, w.scal, s);
+            BP_RET_ON(hipGetLastError());
+            src = list;
+        }
+        // attempt index `round` of the r rejected proofs, into the compact workspace
+        hipbp_prove_input cin{r, n, (const fe25519*)w.v, (const fe25519*)w.gamma, (const fe25519*)(w.scal + 4 * r),
+                              (const fe25519*)(w.scal + (4 + n) * r), (const fe25519*)w.scal};
+        accept_out(r, Lr).view(w.out, &cur);
+        if ((rc = prove_run(&cin, G, H, g, h, ptab, pbits, &cur, stream)) != HIPBP_OK) return rc;
+        m = r;
+    }
+    clk.collect(g_accept_stats.ms);
+    return HIPBP_OK;
+}
+
+int hipbp_batch_generate_range_proof_accepted(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base,
+                                              int max_attempts, int check, const ge25519* G, const ge25519* H,
+                                              const ge25519* g, const ge25519* h, hipbp_proof_out* out,
+                                              uint8_t* attempts, void* stream) {
+    return prove_accepted(in, seed32, index_base, max_attempts, check, G, H, g, h, nullptr, 0, out, attempts, stream);
+}
+
+int hipbp_batch_generate_range_proof_accepted_gens(const hipbp_prove_input* in, const uint8_t* seed32,
+                                                   uint64_t index_base, int max_attempts, int check, void* gens,
+                                                   hipbp_proof_out* out, uint8_t* attempts, void* stream) {
+    Gens* gs = (Gens*)gens;
+    if (int rc = gens_check(gs, in ? in->n : 0, "prover: input n differs from the generator set's")) return rc;
+    return prove_accepted(in, seed32, index_base, max_attempts, check, (const ge25519*)gs->G(), (const ge25519*)gs->H(),
+                          (const ge25519*)gs->g(), (const ge25519*)gs->h(), gs->bits ? gs->tab.as<bp::ge>() : nullptr,
+                          gs->bits, out, attempts, stream);
+}
+
+int hipbp_accepted_last_stats(int* rounds, uint32_t* proved, float* kernel_ms) {
+    if (rounds) *rounds = g_accept_stats.rounds;
+    if (proved) memcpy(proved, g_accept_stats.m, sizeof g_accept_stats.m);
+    if (kernel_ms) memcpy(kernel_ms, g_accept_stats.ms, sizeof g_accept_stats.ms);
+    return HIPBP_OK;
 }
 
 // The seeded prover on host data.  The batch goes through in chunks that alternate over the

@@ -171,6 +171,30 @@ inline void prove_sizes(size_t B, size_t n, bool sort, size_t (&sz)[PB_COUNT]) {
     BP_PROVE_BUFS(BP_BUF_SIZE)
 }
 
+// The accepted prover's retry loop (AcceptWs; n bits, Lr fold rounds), sized at two moments of a
+// round: before its verify for the m proofs it verifies (ok, blk, cnt; r = 0), and after the host
+// has read back the r of them the verifier rejected (m = 0) for what the next round's r proofs
+// need: both index lists (the round reads one and writes the other), their v, gamma, try keys and
+// scalars (rnd | sL | sR, the seeded prover's order), and their proofs as an OutLayout of r.
+// Within a call r only shrinks, so a list that a round still reads is never regrown under it.
+#define BP_ACCEPT_BUFS(X)                                     \
+    X(AB_OK, ok, uint8_t, m)                                  \
+    X(AB_BLK, blk, uint32_t, accept_blocks(m) * U32)          \
+    X(AB_CNT, cnt, uint32_t, U32)                             \
+    X(AB_LIST0, list[0], uint32_t, r * U32)                   \
+    X(AB_LIST1, list[1], uint32_t, r * U32)                   \
+    X(AB_V, v, fe, r * FE)                                    \
+    X(AB_GAMMA, gamma, fe, r * FE)                            \
+    X(AB_KEYS, keys, fe, r * FE)                              \
+    X(AB_SCAL, scal, fe, r * (2 * n + 4) * FE)                \
+    X(AB_OUT, out, uint8_t, r ? accept_out(r, Lr).slot_bytes() : 0)
+enum AcceptBuf { BP_ACCEPT_BUFS(BP_BUF_ID) AB_COUNT };
+inline size_t accept_blocks(size_t m) { return (m + 255) / 256; }   // k_accept_count's blocks (ACCEPT_BLK)
+inline OutLayout accept_out(size_t r, size_t Lr) { return OutLayout{r, r, Lr, 0}; }
+inline void accept_sizes(size_t m, size_t r, size_t n, size_t Lr, size_t (&sz)[AB_COUNT]) {
+    BP_ACCEPT_BUFS(BP_BUF_SIZE)
+}
+
 // One chunk of the stand-alone IPA prover (IpaWs): Bc proofs of n elements, cap = 2n + 2 items each.
 #define BP_IPA_BUFS(X)                            \
     X(IB_A, a, fe, Bc * n * FE)                   \

@@ -11,6 +11,12 @@
 // wraps mod 2^64.  slot 0..3 = alpha, rho, tau1, tau2 (the order of hipbp_prove_input::rnd),
 // 4 + i = sL[i], 4 + n + i = sR[i].
 //
+// The accepted prover's retries draw fresh scalars for attempt a >= 1 of proof p from
+//
+//   key_{p,a} = SHA-256("hipbpProverTryV1" || key_p || LE32(a))          (52 bytes, one block)
+//
+// in place of key_p (key_{p,0} = key_p): scalar(p, a, slot) is seed_scalar on key_{p,a}.
+//
 // Both layouts are __host__ __device__ and written once.  Every field of both messages starts on
 // a 4-byte boundary, so a message is a sequence of big-endian words at compile-time positions.
 // In the device pass the context is sha256_dev.h's register-resident `shaw` (shaw_put,
@@ -21,6 +27,7 @@
 #pragma once
 #include "ge25519_dev.h"   // sha256_dev.h's challenge messages take points
 #include "sha256_dev.h"
+#include "bp_kernels.h"    // ProveOut
 
 namespace bp {
 
@@ -172,10 +179,64 @@ BP_SEED_HD void seed_scalar(uint64_t out[4], const uint64_t key[4], uint32_t slo
     out[3] = (out[3] & 0x7FFFFFFFFFFFFFFFull) | 0x4000000000000000ull;       // d[31] &= 0x7F; d[31] |= 0x40
 }
 
+// key_{p,a}, the key of attempt a of a proof: key_p itself for a = 0, else 52 bytes, one compression
+BP_SEED_HD void seed_try_key(uint64_t out[4], const uint64_t key[4], uint32_t a) {
+    if (a == 0) {
+        out[0] = key[0]; out[1] = key[1]; out[2] = key[2]; out[3] = key[3];
+        return;
+    }
+    seedw c;
+    seed_init(c);
+    seed_tag<0>(c, "hipbpProverTryV1");
+    seed_limbs<16>(c, key);
+    seed_le32<48>(c, a);
+    seed_final<52>(c, out);
+}
+
 // ------------------------------------------------------------------ the derive kernels (bp_prove_seed.hip)
 // keys[B] (workspace), then rnd[B*4], sL[B*n], sR[B*n] in hipbp_prove_input's layout; B (2n + 4) < 2^32.
 // Asynchronous on s; the seed travels in the kernel arguments.
 void launch_seed_derive(const SeedWords& seed, const fe* v, const fe* gamma, uint64_t index_base, uint32_t B,
                         uint32_t n, fe* keys, fe* sL, fe* sR, fe* rnd, hipStream_t s);
+// ... its two launches alone: keys[B], and the scalars of B proofs from keys[B] (key_p or try keys)
+void launch_seed_keys(const SeedWords& seed, const fe* v, const fe* gamma, uint64_t index_base, uint32_t B, uint32_t n,
+                      fe* keys, hipStream_t s);
+void launch_seed_scalars(const fe* keys, uint32_t B, uint32_t n, fe* sL, fe* sR, fe* rnd, hipStream_t s);
+
+// ------------------------------------------------------------------ the accepted prover's kernels
+// out[j] = key_{list[j], a} from keys[] (the batch's key_p), j < m: the retry loop's form.
+void launch_try_keys_list(const fe* keys, const uint32_t* list, uint32_t m, uint32_t a, fe* out, hipStream_t s);
+// out[p] = key_{p, attempt[p]}, p < B (attempt 0 copies the key): the audit entry point's form.
+void launch_try_keys_at(const fe* keys, const uint8_t* attempt, uint32_t B, fe* out, hipStream_t s);
+
+// One round's verdicts.  ok[m], valid[m]: the verifier's verdicts and the prover's valid flags over
+// the round's proofs, proof i of the round being proof src[i] of the batch (src null: i itself, the
+// whole batch in round 1).  A proof with valid and ok is accepted: attempts[p] = round.  One with
+// valid and not ok is rejected; round 1 also writes attempts[p] = 0 for every proof it does not
+// accept.  Two steps with the host's read of *cnt between them:
+//   launch_accept_count: attempts, the rejected proofs per block of 256 into blk[], their exclusive
+//     scan in place and the total into *cnt;
+//   launch_accept_fill: list[k] = the k-th rejected proof's batch index p, ascending, and its
+//     v[p] | gamma[p] gathered into cv[k], cg[k], for k < *cnt.
+// Every output is a function of ok, valid and src alone: no atomics, no launch-to-launch order.
+constexpr uint32_t ACCEPT_BLK = 256;   // proofs per block (the size of blk[] follows: bp_layout.h)
+// the loop's workspace (buffers and sizes: bp_layout.h, BP_ACCEPT_BUFS)
+struct AcceptWs {
+    uint8_t* ok;         // the round's verdicts
+    uint32_t *blk, *cnt;
+    uint32_t* list[2];   // the rejected proofs' batch indices, read and written in turn
+    fe *v, *gamma, *keys, *scal;
+    uint8_t* out;        // the retried proofs, an OutLayout
+};
+void launch_accept_count(const uint8_t* ok, const uint8_t* valid, const uint32_t* src, uint32_t m, uint32_t round,
+                         uint8_t* attempts, uint32_t* blk, uint32_t* cnt, hipStream_t s);
+void launch_accept_fill(const uint8_t* ok, const uint8_t* valid, const uint32_t* src, uint32_t m, const uint32_t* blk,
+                        const fe* v, const fe* gamma, uint32_t* list, fe* cv, fe* cg, hipStream_t s);
+
+// The proofs of a compact sub-batch (src: OutLayout::view with c = m, so the five point arrays, the
+// seven scalar arrays and L | R each lie back to back at stride m) into rows list[j] of the caller's
+// output, all of hipbp_proof_out's fields, in 16-byte pieces.  m (54 + 16 Lr) < 2^32.
+void launch_accept_scatter(const ProveOut& src, const ProveOut& dst, const uint32_t* list, uint32_t m, uint32_t Lr,
+                           hipStream_t s);
 
 }  // namespace bp

@@ -279,6 +279,58 @@ int hipbp_batch_generate_range_proof_seeded(const hipbp_prove_input* in, const u
                                             hipbp_proof_out* out, void* stream);
 int hipbp_batch_generate_range_proof_seeded_gens(const hipbp_prove_input* in, const uint8_t* seed32,
                                                  uint64_t index_base, void* gens, hipbp_proof_out* out, void* stream);
+/* ---- accepted prover (no reference counterpart): the seeded prover, re-proving on the GPU what the
+ * verifier rejects.  The reference's arithmetic makes its own verifier reject a share of honest
+ * proofs (about one in ten at n = 64), and the rejection depends on the nonces, so each rejected
+ * proof is proved again with the scalars of its next try key, byte-exact and little-endian:
+ *   key_{p,0} = key_p
+ *   key_{p,a} = SHA-256("hipbpProverTryV1" || key_p || LE32(a))        a >= 1 (52 bytes)
+ *   scalar(p, a, slot) = the seeded prover's scalar of `slot` under key_{p,a} in place of key_p
+ * Attempt a of proof p depends only on (seed, v_p, gamma_p, index_base + p, n, a), never on the
+ * batch, so a batch cut into several calls yields the single call's proofs and attempts.  The try
+ * key is derived from the secret key_p alone: no new secret, no nonce reused between attempts.
+ *
+ * Round 1 is hipbp_batch_generate_range_proof_seeded into `out` (attempt 0), then the one-shot
+ * batched verify of `out` (check 1: cuda_range_proof_verify semantics, as
+ * hipbp_batch_range_proof_verify; check 2: range_proof_verify semantics, as
+ * hipbp_batch_range_proof_verify_std; V = the proof's own V).  Rounds 2 .. max_attempts (1..16)
+ * prove the rejected proofs again (attempt index round - 1), verify them, and write each new proof
+ * over its row of `out`.  The loop ends when nothing is rejected or after max_attempts rounds.
+ * attempts[p] (DEVICE, [count]) = k >= 1: proof p was accepted at its k-th attempt and `out` holds
+ * that proof (the scalars of key_{p,k-1}).  attempts[p] = 0: valid[p] = 0, the value was refused
+ * (the zeroed proof, never retried), or valid[p] = 1, not accepted within max_attempts (`out`
+ * holds the last attempt's proof).  With max_attempts = 1 the output is the seeded prover's, with
+ * the verifier's verdicts in attempts.
+ *
+ * SYNCHRONOUS, unlike the other device calls: after each round the host waits for `stream` and
+ * reads the number of rejected proofs to size the next round, so the outputs are complete on
+ * return.  The seeded prover's argument checks and limits, made before anything is enqueued (a bad
+ * argument, max_attempts or check, or a null attempts: HIPBP_ERR_ARG, nothing written).  A HIP
+ * error ends the call with HIPBP_ERR_DEVICE and launches nothing more; `out` and attempts are
+ * then undefined.  The retry workspace is kept per (device, stream) and grows with the number of
+ * rejected proofs; hipbp_release_stream_workspaces frees it. */
+int hipbp_batch_generate_range_proof_accepted(const hipbp_prove_input* in, const uint8_t* seed32, uint64_t index_base,
+                                              int max_attempts, int check, const ge25519* G, const ge25519* H,
+                                              const ge25519* g, const ge25519* h, hipbp_proof_out* out,
+                                              uint8_t* attempts, void* stream);
+/* The same with a generator set: its generators; its prefix tables for the prover in both checks
+ * and for the verify in check 1 (where the one-shot verify takes them,
+ * hipbp_batch_range_proof_verify_gens); check 2 verifies without tables.  Same bits either way. */
+int hipbp_batch_generate_range_proof_accepted_gens(const hipbp_prove_input* in, const uint8_t* seed32,
+                                                   uint64_t index_base, int max_attempts, int check, void* gens,
+                                                   hipbp_proof_out* out, uint8_t* attempts, void* stream);
+/* hipbp_derive_prover_scalars for chosen attempts: proof p's scalars under key_{p, attempt[p]}
+ * (attempt: DEVICE [count], 0-based; NULL: all 0, hipbp_derive_prover_scalars itself).  With
+ * attempt[p] = max(attempts[p], 1) - 1 these are the scalars the accepted prover's output was
+ * proved with.  Asynchronous on `stream`; the same checks. */
+int hipbp_derive_prover_scalars_at(const uint8_t* seed32, const fe25519* v, const fe25519* gamma, uint64_t index_base,
+                                   const uint8_t* attempt, size_t count, size_t n, fe25519* sL, fe25519* sR,
+                                   fe25519* rnd, void* stream);
+/* What the calling thread's last accepted call did (for benchmarks): its rounds, the proofs proved
+ * in each (proved[16]; proved[0] = count) and, when HIPBP_ACCEPT_TIMING=1 was set, the HIP-event
+ * times in ms of the loop's own kernels summed over the rounds (kernel_ms[3]: k_try_keys,
+ * k_accept_select's launches, k_accept_scatter).  Any pointer may be NULL. */
+int hipbp_accepted_last_stats(int* rounds, uint32_t* proved, float* kernel_ms);
 /* The seeded prover on host data: proofs[i] = the proof of (v[i], gamma[i]) under seed32 at index
  * index_base + i, for i < count, with the bytes the device call gives.  Host pointers, synchronous,
  * on the calling thread's current device.  n: power of two, 1..128, G->length = H->length = n.
@@ -408,7 +460,7 @@ int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_
  * in0..in3 in raw limb order.  For checking against FIPS 180-4 (bulletproof_challenge.cu:6-77). */
 int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
- * point-tree, prover, the seeded prover's scalars and keys, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
+ * point-tree, prover, the seeded prover's scalars and keys, the accepted prover's retry workspace, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
  * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
  * a caller that makes short-lived streams calls this before destroying one.  No reference
  * counterpart. */
