@@ -16,6 +16,15 @@
  * The types are layout-identical to the reference's (curve25519_ops.h:15-25,
  * bulletproof_vectors.h:8-17, :65-74, bulletproof_range_proof.h:7-18); when the
  * reference headers are included first, theirs are used.
+ *
+ * Points are taken as given, as the reference takes them: a ge25519 is sixteen limbs,
+ * any limbs.  Z need not be 1, T need not be X*Y, no coordinate need be below p; the
+ * result has the bits the reference's arithmetic gives on those limbs.  This holds for
+ * every point argument: MSM points, generators (with or without prefix tables), proof
+ * points, Pippenger inputs.  The kernels' Z = 1 shortcuts test exact limb equality
+ * (1, 0, 0, 0), wave-uniformly, so p + 1 or 1 + 2^255 take the general product.  Pinned by
+ * tests/test_projective_points.py against the reference's own outputs
+ * (tests/golden/projective.npz, point.npz) and the CPU restatement.
  */
 #ifndef CUDABULLETPROOF_HIP_H
 #define CUDABULLETPROOF_HIP_H

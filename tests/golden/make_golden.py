@@ -28,7 +28,20 @@ oracle/build_ref.sh) and records inputs + reference outputs as .npz (no pickles)
               + 256 tampered copies, the reference's cuda_range_proof_verify outcome of each
               (verdict, early reject, 8-byte digests of the proof, P and the check point).
 
-  python tests/golden/make_golden.py [ipa4096|rpverify|accept|printed|batch1024]
+  projective.npz points taken as given: inputs from the builder in tests/test_projective_points.py
+              (Z of every class: 1, p+1, 2p+1, 1+2^255, 0, 2, p, p-1, 2^256-1, random; X, Y, T full
+              256-bit words and edge limbs; T arbitrary on half the projective points).  msm_canon at
+              n in {1, 5, 64, 130}, every class present at n >= 64; a Z = 0 point there has a zero
+              scalar, because with a full-length scalar its term is (0, 0, 1, 0) and absorbs the sum:
+              row 5z, the n = 5 row with one Z zeroed and that scalar's bit 255 set, records that.
+              One generator set at n = 16 (G
+              projective, H alternating, g.Z = p+1, h.Z random; no Z = 0) with four reference proofs (seed, value) and four proof-shaped random
+              inputs: the cuda_range_proof_verify verdict and early-reject flag, P, the check point,
+              the range_proof_verify verdict, delta and sub-check flags (as rpverify.npz); two
+              inner_product_prove cases (n = 1, 8; projective G, H, Q) with their inputs, in
+              ipa_prove.npz's layout under the prefix ipa_.
+
+  python tests/golden/make_golden.py [ipa4096|rpverify|accept|printed|batch1024|projective]
               (argument: regenerate only that fixture)
 
 The survey's golden digests are reproduced by tests/test_oracle_golden.py.
@@ -502,8 +515,86 @@ def make_batch1024(procs=8):
     print(f"batch1024: {int(out['ok'].sum())}/{B} reference accepts, tampered {int(out['t_ok'].sum())}/256 accepts")
 
 
+def make_projective():
+    """projective.npz: the reference on points that are not affine (Z != 1, T != X*Y, coordinates
+    above p), drawn by the builder of tests/test_projective_points.py."""
+    po.build()
+    R = po.Reference()
+    sys.path.insert(0, os.path.dirname(HERE))
+    import make_ipa_prove
+    import test_projective_points as tp
+    rng = np.random.default_rng(20260219)
+    C = np.ascontiguousarray
+    out = {}
+    for n in (1, 5, 64, 130):
+        zc = tp.msm_classes(rng, n)
+        Pn = tp.proj_points(rng, zc)
+        s = tp.park_zero_z(edge_fe(rng, n), zc)    # Z = 0 with a non-zero scalar absorbs the sum: row 5z
+        out[f"msm_P{n}"], out[f"msm_s{n}"], out[f"msm_canon{n}"] = Pn, s, R.msm("msm_canon", s, Pn)
+    Pz, sz = out["msm_P5"].copy(), out["msm_s5"].copy()
+    Pz[2, 8:12] = 0
+    sz[2] = tp.rand256(rng, 1)[0] | np.array([0, 0, 0, 1 << 63], np.uint64)
+    out["msm_P5z"], out["msm_s5z"], out["msm_canon5z"] = Pz, sz, R.msm("msm_canon", sz, Pz)
+    n = 16
+    G, H, g, h = tp.gen_set(rng, n)
+    cases, seeds, vals = [], [], []
+    for seed in range(401, 405):
+        val = np.zeros(32, np.uint8)
+        val[:n // 8] = rng.integers(0, 256, n // 8)
+        cases.append(R.prove(seed, val, n, G, H, g, h))
+        seeds.append(seed)
+        vals.append(val)
+    arr = tp.proof_shaped(rng, n, 4)
+    heads = tp.heads_of(arr)
+    for p in range(4):
+        cases.append(dict(head=C(heads[p]), V=C(arr["V"][p]), a=C(arr["a"][p]), b=C(arr["b"][p]), L=C(arr["L"][p]),
+                          R=C(arr["R"][p])))
+    rec = {k: [] for k in ("ok_cuda", "early", "P", "check", "ok_cpu", "delta", "flags")}
+    for pr in cases:
+        ok, txt = R.cuda_range_proof_verify_log(pr, n, G, H, g, h)
+        hd = po.head_fields(pr["head"])
+        _, _, chk = R.ipa_fold(G, H, n, hd["x"], pr["L"], pr["R"], pr["a"][0], pr["b"][0], hd["c"], h)
+        delta, flags = R.rpv_parts(pr, n, G, H, g, h)
+        for k, v in zip(rec, (ok, po.printed_stats(txt)["early_reject"], R.verify_P(pr, n, G, H, g, h)[0], chk,
+                              R.range_proof_verify(pr, n, G, H, g, h), delta, flags)):
+            rec[k].append(v)
+    out.update(G=G, H=H, g=g, h=h, seed=np.array(seeds, np.int64), value=np.stack(vals),
+               **{k: np.stack([pr[k] for pr in cases]) for k in ("head", "V", "a", "b", "L", "R")},
+               **{k: np.stack([np.asarray(x) for x in v]) for k, v in rec.items()})
+    # inner_product_prove over projective G, H, Q: the inputs, then ipa_prove.npz's layout
+    recs, ins = [], {k: [] for k in ("a_in", "b_in", "G", "H", "Q", "tr")}
+    for m in (1, 8):
+        a, b = tp.rand256(rng, m, top=False), tp.rand256(rng, m, top=False)
+        Gm = tp.proj_points(rng, tp.live_cycle(m))
+        Hm = tp.proj_points(rng, [(0, tp.ZC["2p+1"], tp.ZC["rand256"])[i % 3] for i in range(m)])
+        Q = tp.proj_points(rng, [tp.ZC["1+2^255"]])[0]
+        tr = rng.integers(0, 256, 32).astype(np.uint8)
+        c_in = po.fe()
+        R.f("inner_product")(po._p(c_in), po._p(a), po._p(b), po._sz(m))
+        pr = R.ipa_prove(a, b, Gm, Hm, Q, c_in, tr)
+        c_final = po.fe()
+        R.f("inner_product")(po._p(c_final), po._p(pr["a"]), po._p(pr["b"]), po._sz(1))
+        Pm = R.msm("msm_canon", np.concatenate([a, b]), np.concatenate([Gm, Hm]))
+        ok_in = R.cuda_inner_product_verify(m, pr["a"], pr["b"], c_in, pr["L"], pr["R"], pr["x"], Pm, Gm, Hm, Q)
+        ok_final = R.cuda_inner_product_verify(m, pr["a"], pr["b"], c_final, pr["L"], pr["R"], pr["x"], Pm, Gm, Hm, Q)
+        _, _, chk = R.ipa_fold(Gm, Hm, m, pr["x"], pr["L"], pr["R"], pr["a"][0], pr["b"][0], c_final, Q)
+        recs.append(dict(a=pr["a"][0], b=pr["b"][0], x=pr["x"], c_in=c_in, c_final=c_final, L=pr["L"].reshape(-1, 16),
+                         R=pr["R"].reshape(-1, 16), P=Pm, ok_in=ok_in, ok_final=ok_final, check=chk))
+        for k, v in zip(ins, (a, b, Gm, Hm, Q[None], tr[None])):
+            ins[k].append(v)
+    out["ipa_n"] = np.array([1, 8], np.int64)
+    out.update({"ipa_" + k: v for k, v in make_ipa_prove.pack(recs).items()})
+    out.update({"ipa_" + k: np.concatenate(v) for k, v in ins.items()})
+    np.savez_compressed(os.path.join(HERE, "projective.npz"), **out)
+    print(f"projective: verdicts cuda {out['ok_cuda'].astype(int).tolist()} cpu {out['ok_cpu'].astype(int).tolist()} "
+          f"early {out['early'].astype(int).tolist()} flags {out['flags'].tolist()}; "
+          f"ipa ok_in {out['ipa_ok_in'].tolist()} ok_final {out['ipa_ok_final'].tolist()}")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["batch1024"]:
+    if sys.argv[1:] == ["projective"]:
+        make_projective()
+    elif sys.argv[1:] == ["batch1024"]:
         make_batch1024()
     elif sys.argv[1:] == ["ipa4096"]:
         make_ipa4096()

@@ -187,6 +187,56 @@ def test_oracle_batch1024_sample(oracle, golden):
         check(pr, d["t_ok"][j], d["t_P_d8"][j], d["t_check_d8"][j], d["t_early"][j])
 
 
+def test_projective_against_reference(oracle, golden):
+    """projective.npz (points taken as given: Z of every class, arbitrary T, coordinates above p):
+    the reference's msm_canon rows; its verdicts, P, check points and range_proof_verify sub-checks
+    on eight cases under a projective generator set; its four proofs byte for byte; its two
+    inner-product proofs' commitments, verdicts and check points."""
+    from oracle.pyoracle import prover_randomness
+    d = golden("projective")
+    for n in (1, 5, 64, 130):
+        assert np.array_equal(oracle.msm_canon(d[f"msm_s{n}"], d[f"msm_P{n}"]), d[f"msm_canon{n}"]), n
+        assert d[f"msm_canon{n}"][:8].any(), n        # not the absorbing point (0, 0, 1, 0) ...
+    assert np.array_equal(oracle.msm_canon(d["msm_s5z"], d["msm_P5z"]), d["msm_canon5z"])
+    assert not d["msm_canon5z"][:8].any()             # ... which one Z = 0 term of a long scalar makes it
+    n = 16
+    G, H, g, h = d["G"], d["H"], d["g"], d["h"]
+    one = np.array([1, 0, 0, 0], np.uint64)
+    assert not (G[:, 8:12] == one).all(axis=1).any() and (H[0::2, 8:12] == one).all()
+    assert d["P"][:, :8].any(axis=1).all() and d["check"][:, :8].any(axis=1).all()
+    for i in range(len(d["head"])):
+        args = (d["head"][i], d["V"][i], n, d["a"][i], d["b"][i], d["L"][i], d["R"][i], G, H, g, h)
+        ok, P, chk, _, _ = oracle.cuda_range_proof_verify(*args)
+        assert ok == bool(d["ok_cuda"][i]), i
+        assert np.array_equal(P, d["P"][i]), i
+        if not d["early"][i]:
+            assert np.array_equal(chk, d["check"][i]), i
+        ok2, det = oracle.range_proof_verify(*args)
+        f = int(det["range_ok"]) | int(det["poly_ok"]) << 1 | int(det["ip_ok"]) << 2
+        assert ok2 == bool(d["ok_cpu"][i]), i
+        assert f == int(d["flags"][i]), i
+        assert np.array_equal(det["delta"], d["delta"][i]), i
+    for i, seed in enumerate(d["seed"]):
+        gamma, sLR, rnd4 = prover_randomness(int(seed), n)
+        pr = oracle.generate_range_proof(d["value"][i], gamma, sLR, rnd4, n, G, H, g, h)
+        assert np.array_equal(pr["head"], d["head"][i]), i
+        for k in ("V", "a", "b", "L", "R"):
+            assert np.array_equal(pr[k], d[k][i]), (i, k)
+    ns = [int(x) for x in d["ipa_n"]]
+    for k, m in enumerate(ns):
+        o, lo = sum(ns[:k]), d["ipa_L_off"]
+        a, b, Gm, Hm = (d["ipa_" + key][o:o + m] for key in ("a_in", "b_in", "G", "H"))
+        Q, L, R = d["ipa_Q"][k], d["ipa_L"][lo[k]:lo[k + 1]], d["ipa_R"][lo[k]:lo[k + 1]]
+        assert np.array_equal(oracle.inner_product(a, b), d["ipa_c_in"][k]), k
+        assert np.array_equal(oracle.msm_canon(np.concatenate([a, b]), np.concatenate([Gm, Hm])), d["ipa_P"][k]), k
+        for which in ("final", "in"):
+            ok, chk, _, _ = oracle.cuda_inner_product_verify(m, d["ipa_a"][k], d["ipa_b"][k], d["ipa_c_" + which][k],
+                                                             L, R, d["ipa_x"][k], d["ipa_P"][k], Gm, Hm, Q)
+            assert ok == bool(d["ipa_ok_" + which][k]), (k, which)
+            if which == "final":
+                assert np.array_equal(chk, d["ipa_check"][k]), k
+
+
 def test_prover_refuses_out_of_range(oracle):
     """validate_range_input (rp.cu:238): bit n or any higher byte set -> no proof."""
     from oracle.pyoracle import prover_randomness
