@@ -120,7 +120,7 @@ EXPORTS = [
     "hipbp_batch_range_proof_verify_std", "hipbp_batch_range_proof_verify_gens", "hipbp_batch_inner_product_verify", "hipbp_batch_generate_range_proof", "hipbp_msm",
     "hipbp_msm_pippenger", "hipbp_msm_pippenger_batch", "hipbp_msm_pippenger_windows",
     "hipbp_msm_pippenger_horner", "hipbp_msm_batch", "hipbp_msm_batch_gens", "hipbp_point_tree", "hipbp_field_op",
-    "hipbp_sha_probe", "hipbp_sync", "hipbp_timing_enable",
+    "hipbp_sha_probe", "hipbp_sm_probe", "hipbp_sync", "hipbp_timing_enable",
     "hipbp_timing_collect", "hipbp_kernel_count", "hipbp_kernel_name", "hipbp_pipeline_create",
     "hipbp_pipeline_push", "hipbp_pipeline_flush", "hipbp_pipeline_depth", "hipbp_pipeline_destroy",
     "hipbp_pipeline_defer_msm",
@@ -155,7 +155,7 @@ def lib():
                   "hipbp_batch_inner_product_verify", "hipbp_batch_generate_range_proof", "hipbp_msm",
                   "hipbp_msm_pippenger", "hipbp_msm_pippenger_batch", "hipbp_msm_pippenger_windows",
                   "hipbp_msm_pippenger_horner", "hipbp_msm_batch", "hipbp_msm_batch_gens", "hipbp_point_tree",
-                  "hipbp_field_op", "hipbp_sha_probe", "hipbp_sync", "hipbp_device_count",
+                  "hipbp_field_op", "hipbp_sha_probe", "hipbp_sm_probe", "hipbp_sync", "hipbp_device_count",
                   "hipbp_release_stream_workspaces", "hipbp_batch_inner_product_prove",
                   "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host",
                   "hipbp_derive_prover_scalars", "hipbp_batch_generate_range_proof_seeded",
@@ -838,9 +838,19 @@ def field_op(op, r, a, b=None, stream=None):
            "mul_q4_k": 12,   # 12: the same split over a lane quad (fe_mul_q4_k, the drain forms' C)
            # the row step's latency forms (13, 15/16, 19) and deferred rare-edge forms (14, 17/18, 20)
            "add_lat": 13, "add_defer": 14, "addsub_lat_add": 15, "addsub_lat_sub": 16,
-           "addsub_defer_add": 17, "addsub_defer_sub": 18, "fold_lat": 19, "fold_defer": 20}
+           "addsub_defer_add": 17, "addsub_defer_sub": 18, "fold_lat": 19, "fold_defer": 20,
+           # the lane loops' deferred forms (ge25519_dev.h), recomputed per element on an edge or a failed gate
+           "add_acc": 21, "addsub_acc_add": 22, "addsub_acc_sub": 23, "fold_acc": 24, "mul_acc": 25, "sq_acc": 26,
+           "sub_acc": 27}
     _chk(lib().hipbp_field_op(ops[op], _c(r.data_ptr()), _c(a.data_ptr()), _c(b.data_ptr()) if b is not None else None,
                               _sz(a.shape[0]), _stream_ptr(stream)))
+
+
+def sm_probe(force, out, scalars, points, stream=None):
+    """hipbp_sm_probe: out[i] (N, 16) = scalarmult(scalars[i] (N, 4), points[i] (N, 16)), raw extended
+    points; force: through the deferred pass's recovery path (the same bits)."""
+    _chk(lib().hipbp_sm_probe(int(bool(force)), _c(out.data_ptr()), _c(scalars.data_ptr()), _c(points.data_ptr()),
+                              _sz(scalars.shape[0]), _stream_ptr(stream)))
 
 
 def sha_probe(kind, out, inp, stream=None):

@@ -1638,14 +1638,24 @@ int hipbp_point_tree(ge25519* result, const ge25519* points, size_t n, void* str
 
 int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_t count, void* stream) {
     BP_ENGINE_OR_RET(e);
-    if (op < 0 || op > 20) { g_err = "bad op"; return HIPBP_ERR_ARG; }
-    if (!a || (!b && op != 3 && op != 5 && op != 7 && op != 11 && op != 12)) { g_err = "null operand"; return HIPBP_ERR_ARG; }
+    if (op < 0 || op > 27) { g_err = "bad op"; return HIPBP_ERR_ARG; }
+    if (!a || (!b && op != 3 && op != 5 && op != 7 && op != 11 && op != 12 && op != 26)) { g_err = "null operand"; return HIPBP_ERR_ARG; }
     if (count == 0) return HIPBP_OK;
     hipStream_t s = pick(stream);
     if (op == 5)
         bp::launch_invert((bp::fe*)r, (const bp::fe*)a, count, s);
     else
         bp::launch_field_op(op, (bp::fe*)r, (const bp::fe*)a, (const bp::fe*)b, count, s);
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_sm_probe(int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count, void* stream) {
+    BP_ENGINE_OR_RET(e);
+    if (!out || !scalars || !points) { g_err = "null operand"; return HIPBP_ERR_ARG; }
+    if (count == 0) return HIPBP_OK;
+    bp::launch_sm_probe(force != 0, (bp::ge*)out, (const bp::fe*)scalars, (const bp::ge*)points, count, e->dtab,
+                        pick(stream));
     BP_RET_ON(hipGetLastError());
     return HIPBP_OK;
 }

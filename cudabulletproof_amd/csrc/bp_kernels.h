@@ -350,6 +350,8 @@ void launch_ipa_final(const IpaWs& ws, const fe* c_in, fe* a, fe* b, fe* c, fe* 
 // Elementwise field ops: op 0 add, 1 sub, 2 mul, 3 square-kernel quirk, 4 soa add (limbwise, no carry)
 void launch_field_op(int op, fe* r, const fe* a, const fe* b, size_t count, hipStream_t s);
 void launch_sha_probe(int kind, fe* out, const fe* in, size_t count, hipStream_t s);
+// out[i] = scalarmult(s[i], P[i]) (raw); force: through the deferred pass's recovery path
+void launch_sm_probe(int force, ge* out, const fe* s, const ge* P, size_t count, const ge* dtab, hipStream_t st);
 void launch_ip_shared(fe* out, const fe* a, const fe* b, size_t n, hipStream_t s);
 void launch_ip_grid(fe* out, fe* part, const fe* a, const fe* b, size_t n, hipStream_t s);
 void launch_ip_batch(fe* out, const fe* a, const fe* b, size_t n, size_t nvec, hipStream_t s);

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(TPB) void k_field_op(int op, fe* r, const fe* __res
     }
     if (i >= count) return;
     fe x = a[i], y;
-    if (op != 3 && op != 7 && op != 11) y = b[i];   // unary ops take no b
+    if (op != 3 && op != 7 && op != 11 && op != 26) y = b[i];   // unary ops take no b
     fe z;
     switch (op) {
         case 0: z = fe_add(x, y); break;
@@ -399,6 +399,49 @@ __global__ __launch_bounds__(TPB) void k_field_op(int op, fe* r, const fe* __res
             }
             break;
         }
+        // the lane loops' deferred forms (LAT 3: the throughput blocks' fast statements, the bounded
+        // products with the gate's words max-ed into gacc), here per element: the gated form
+        // recomputes the result when the element's running words report an edge or a failed gate
+        case 21: {
+            uint32_t acc = 0;
+            z = fe_add<3>(x, y, &acc);
+            if (acc == 0xFFFFFFFFu) z = fe_add(x, y);
+            break;
+        }
+        case 22:
+        case 23: {
+            fe sm, df;
+            uint32_t acc = 0;
+            fe_addsub<3>(x, y, sm, df, &acc);
+            if (acc == 0xFFFFFFFFu) fe_addsub(x, y, sm, df);
+            z = op == 22 ? sm : df;
+            break;
+        }
+        case 24: {
+            uint64_t t[8] = {x.v[0], x.v[1], x.v[2], x.v[3], y.v[0], y.v[1], y.v[2], y.v[3]};
+            uint32_t acc = 0;
+            z = fe_fold512<3>(t, &acc);
+            if (acc == 0xFFFFFFFFu) z = fe_fold512(t);
+            break;
+        }
+        case 25: {
+            Defer d;
+            z = fe_mul<3>(x, y, &d.acc, &d.gacc);
+            if (d.acc == 0xFFFFFFFFu || d.gacc > MUL_BOUNDED_WORD) z = fe_mul(x, y);
+            break;
+        }
+        case 26: {
+            Defer d;
+            z = fe_sq<3>(x, &d.acc, &d.gacc);
+            if (d.acc == 0xFFFFFFFFu || d.gacc > MUL_BOUNDED_WORD) z = fe_sq(x);
+            break;
+        }
+        case 27: {
+            uint32_t acc = 0;
+            z = fe_sub<3>(x, y, &acc);
+            if (acc == 0xFFFFFFFFu) z = fe_sub(x, y);
+            break;
+        }
         default:
 #pragma unroll
             for (int k = 0; k < 4; k++) z.v[k] = x.v[k] + y.v[k];
@@ -425,6 +468,24 @@ __global__ __launch_bounds__(TPB) void k_sha_probe(int kind, fe* out, const fe* 
         default: r = sha_4fe(f[0], f[1], f[2], f[3]); break;      // crv:330-344, rp.cu:560-566
     }
     out[i] = r;
+}
+
+// ge25519_scalarmult through the one call site every kernel uses (ge25519_dev.h scalarmult), item i
+// = s[i] * P[i], the raw extended result.  `force`: the loops' deferred pass reports a hit after its
+// first chunk whatever the data, so ordinary inputs take the recovery path (the rerun with the gated
+// forms); the results must be the same bits either way (hipbp_sm_probe, tests/test_lane_defer_gpu.py).
+__global__ __launch_bounds__(TPB) void k_sm_probe(int force, ge* out, const fe* __restrict__ s, const ge* __restrict__ P,
+                                                  size_t count, const ge* __restrict__ dtab) {
+    __shared__ geq qs[TPB];
+    const size_t i = gid();
+    if (i >= count) return;
+    out[i] = force ? scalarmult<true, true>(s[i], P[i], &qs[threadIdx.x], dtab)
+                   : scalarmult<true, false>(s[i], P[i], &qs[threadIdx.x], dtab);
+}
+
+void launch_sm_probe(int force, ge* out, const fe* s, const ge* P, size_t count, const ge* dtab, hipStream_t st) {
+    if (count == 0) return;
+    k_sm_probe<<<nblk(count), TPB, 0, st>>>(force, out, s, P, count, dtab);
 }
 
 void launch_sha_probe(int kind, fe* out, const fe* in, size_t count, hipStream_t s) {

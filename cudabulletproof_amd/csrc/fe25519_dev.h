@@ -127,7 +127,9 @@ BP_DEV uint64_t cat64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64
 // fe25519_add (curve25519_ops.cu:41-68): exact 257-bit sum (one 32-bit carry chain), then
 // one lossy "- p" when the sum carried out or is >= p.
 // LAT 1: the latency form of the generated block (field_asm.h fe_add_asm_lat, the 16-lane row step);
-// LAT 2: its fast statement alone, the rare-edge test deferred into *acc (fe_add_asm_lat_acc).
+// LAT 2: its fast statement alone, the rare-edge test deferred into *acc (fe_add_asm_lat_acc);
+// LAT 3: the throughput block's fast statement alone, deferred the same way (fe_add_asm_acc: the lane
+// loops' deferred point forms, ge25519_dev.h).
 template <int LAT = 0>
 BP_DEV fe fe_add(const fe& f, const fe& g, uint32_t* acc = nullptr) {
 #if BP_FIELD_ASM && defined(__HIP_DEVICE_COMPILE__)   // generated gfx950 form (field_asm.h), same bits
@@ -137,7 +139,7 @@ BP_DEV fe fe_add(const fe& f, const fe& g, uint32_t* acc = nullptr) {
         a[2 * i] = lo32(f.v[i]); a[2 * i + 1] = hi32(f.v[i]);
         b[2 * i] = lo32(g.v[i]); b[2 * i + 1] = hi32(g.v[i]);
     }
-    if constexpr (LAT == 2) fe_add_asm_lat_acc(o, a, b, *acc); else if constexpr (LAT == 1) fe_add_asm_lat(o, a, b); else fe_add_asm(o, a, b);
+    if constexpr (LAT == 3) fe_add_asm_acc(o, a, b, *acc); else if constexpr (LAT == 2) fe_add_asm_lat_acc(o, a, b, *acc); else if constexpr (LAT == 1) fe_add_asm_lat(o, a, b); else fe_add_asm(o, a, b);
     return fe{{cat64(o[0], o[1]), cat64(o[2], o[3]), cat64(o[4], o[5]), cat64(o[6], o[7])}};
 #else
     fe h;
@@ -157,7 +159,9 @@ BP_DEV fe fe_add(const fe& f, const fe& g, uint32_t* acc = nullptr) {
 // to 0 and the borrow is dropped).  Then, on a final borrow, the literal "+ p" pass:
 //   a0 = t0 + p0, cy = a0 < p0 (= t0 >= 19);  a_i = t_i + lo64(p_i + cy), cy = a_i < p_i
 // i.e. a_i = cy ? t_i : t_i - 1 and cy = a_i != 2^64-1 for i = 1, 2;  a3 = t3 + p3 + cy.
-BP_DEV fe fe_sub(const fe& f, const fe& g) {
+// LAT 3: the fast statement alone, the rare-edge test deferred into *acc (fe_sub_asm_acc).
+template <int LAT = 0>
+BP_DEV fe fe_sub(const fe& f, const fe& g, uint32_t* acc = nullptr) {
 #if BP_FIELD_ASM && defined(__HIP_DEVICE_COMPILE__)   // generated gfx950 form (field_asm.h), same bits
     uint32_t a[8], b[8], o[8];
 #pragma unroll
@@ -165,7 +169,7 @@ BP_DEV fe fe_sub(const fe& f, const fe& g) {
         a[2 * i] = lo32(f.v[i]); a[2 * i + 1] = hi32(f.v[i]);
         b[2 * i] = lo32(g.v[i]); b[2 * i + 1] = hi32(g.v[i]);
     }
-    fe_sub_asm(o, a, b);
+    if constexpr (LAT == 3) fe_sub_asm_acc(o, a, b, *acc); else fe_sub_asm(o, a, b);
     return fe{{cat64(o[0], o[1]), cat64(o[2], o[3]), cat64(o[4], o[5]), cat64(o[6], o[7])}};
 #else
     fe t;
@@ -202,7 +206,8 @@ BP_DEV void fe_addsub(const fe& f, const fe& g, fe& sum, fe& diff, uint32_t* acc
         a[2 * i] = lo32(f.v[i]); a[2 * i + 1] = hi32(f.v[i]);
         b[2 * i] = lo32(g.v[i]); b[2 * i + 1] = hi32(g.v[i]);
     }
-    if constexpr (LAT == 2) fe_addsub_asm_lat_acc(os, od, a, b, *acc);
+    if constexpr (LAT == 3) fe_addsub_asm_acc(os, od, a, b, *acc);
+    else if constexpr (LAT == 2) fe_addsub_asm_lat_acc(os, od, a, b, *acc);
     else if constexpr (LAT == 1) fe_addsub_asm_lat(os, od, a, b);
     else fe_addsub_asm(os, od, a, b);
     sum = fe{{cat64(os[0], os[1]), cat64(os[2], os[3]), cat64(os[4], os[5]), cat64(os[6], os[7])}};
@@ -229,7 +234,7 @@ BP_DEV fe fe_fold512(const uint64_t t[8], uint32_t* acc = nullptr) {
         a[2 * i] = lo32(t[i]); a[2 * i + 1] = hi32(t[i]);
         xh[2 * i] = lo32(x); xh[2 * i + 1] = hi32(x);
     }
-    if constexpr (LAT == 2) fe_fold_asm_lat_acc(o, a, xh, *acc); else if constexpr (LAT == 1) fe_fold_asm_lat(o, a, xh); else fe_fold_asm(o, a, xh);
+    if constexpr (LAT == 3) fe_fold_asm_acc(o, a, xh, *acc); else if constexpr (LAT == 2) fe_fold_asm_lat_acc(o, a, xh, *acc); else if constexpr (LAT == 1) fe_fold_asm_lat(o, a, xh); else fe_fold_asm(o, a, xh);
     return fe{{cat64(o[0], o[1]), cat64(o[2], o[3]), cat64(o[4], o[5]), cat64(o[6], o[7])}};
 #else
     fe h;
@@ -251,7 +256,20 @@ BP_DEV fe fe_fold512(const uint64_t t[8], uint32_t* acc = nullptr) {
 // 96-bit column accumulator.  BP_MUL_ASM selects the generated gfx950 column kernels
 // (mul512_asm.h: v_mad_u64_u32 carry-out + v_addc_co_u32, 2 VALU per 32x32 product);
 // the plain-C form below is the reference formulation of the same product.
-BP_DEV void mul512(uint64_t t[8], const fe& f, const fe& g) {
+// DEFER: the bounded form only, the gating words max-ed into the caller's running *gacc (one
+// v_max3_u32, no ballot, no branch): a lane whose gate fails shows as gacc > MUL_BOUNDED_WORD and the
+// caller recomputes with the gated form (the lane loops' deferred pass, ge25519_dev.h).
+BP_DEV void mul_gate_defer(uint32_t& gacc, uint32_t x, uint32_t y) {
+#ifdef __HIP_DEVICE_COMPILE__
+    asm("v_max3_u32 %0, %0, %1, %2" : "+v"(gacc) : "v"(x), "v"(y));
+#else
+    gacc = x > gacc ? x : gacc;
+    gacc = y > gacc ? y : gacc;
+#endif
+}
+
+template <bool DEFER = false>
+BP_DEV void mul512(uint64_t t[8], const fe& f, const fe& g, uint32_t* gacc = nullptr) {
     uint32_t a[8], b[8], w[16];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -268,7 +286,8 @@ BP_DEV void mul512(uint64_t t[8], const fe& f, const fe& g) {
     // this arithmetic's values are not reduced below 2^255, so that gate failed in most waves,
     // profiles/ab/r05d_bounded2.json.)
     mul512_bounded_asm(w, a, b);
-    if (__builtin_expect(__any(max(a[0], b[7]) > MUL_BOUNDED_WORD), 0)) mul512_asm(w, a, b);
+    if constexpr (DEFER) mul_gate_defer(*gacc, a[0], b[7]);
+    else if (__builtin_expect(__any(max(a[0], b[7]) > MUL_BOUNDED_WORD), 0)) mul512_asm(w, a, b);
 #else
     uint64_t acc = 0;
     uint32_t c2 = 0;
@@ -293,15 +312,22 @@ BP_DEV void mul512(uint64_t t[8], const fe& f, const fe& g) {
 }
 
 // fe25519_mul (curve25519_ops.cu:93-146 == device_curve25519_ops.cuh:117-171)
-BP_DEV fe fe_mul(const fe& f, const fe& g) {
+// LAT 3 (with acc, gacc): the deferred forms of the product's gate and of the fold's rare-edge test.
+// BP_DEFER_GATES 0 keeps the gate inline in the LAT 3 forms (an A/B build: edges deferred only).
+#ifndef BP_DEFER_GATES
+#define BP_DEFER_GATES 1
+#endif
+template <int LAT = 0>
+BP_DEV fe fe_mul(const fe& f, const fe& g, uint32_t* acc = nullptr, uint32_t* gacc = nullptr) {
     uint64_t t[8];
-    mul512(t, f, g);
-    return fe_fold512(t);
+    mul512<LAT == 3 && BP_DEFER_GATES>(t, f, g, gacc);
+    return fe_fold512<LAT>(t, acc);
 }
 
 // Exact 512-bit square: 2 * (off-diagonal products, 28 of them) + the 8 diagonal squares —
 // the same 512 bits as mul512(t, f, f) with 36 instead of 64 32x32 products.
-BP_DEV void sqr512(uint64_t t[8], const fe& f) {
+template <bool DEFER = false>
+BP_DEV void sqr512(uint64_t t[8], const fe& f, uint32_t* gacc = nullptr) {
     uint32_t a[8], o[16], w[16];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -310,7 +336,8 @@ BP_DEV void sqr512(uint64_t t[8], const fe& f) {
     }
 #if BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     sqr512_offdiag_bounded_asm(o, a);
-    if (__builtin_expect(__any(max(a[0], a[7]) > MUL_BOUNDED_WORD), 0)) sqr512_offdiag_asm(o, a);
+    if constexpr (DEFER) mul_gate_defer(*gacc, a[0], a[7]);
+    else if (__builtin_expect(__any(max(a[0], a[7]) > MUL_BOUNDED_WORD), 0)) sqr512_offdiag_asm(o, a);
 #else
     uint64_t acc = 0;
     uint32_t c2 = 0;
@@ -350,10 +377,11 @@ BP_DEV void sqr512(uint64_t t[8], const fe& f) {
 }
 
 // fe25519_sq (curve25519_ops.cu:149) == mul(f, f): the same exact product, then the same fold.
-BP_DEV fe fe_sq(const fe& f) {
+template <int LAT = 0>
+BP_DEV fe fe_sq(const fe& f, uint32_t* acc = nullptr, uint32_t* gacc = nullptr) {
     uint64_t t[8];
-    sqr512(t, f);
-    return fe_fold512(t);
+    sqr512<LAT == 3 && BP_DEFER_GATES>(t, f, gacc);
+    return fe_fold512<LAT>(t, acc);
 }
 
 // mul by 1 (device_curve25519_ops.cuh:260 with z_inv = 1): product has zero upper half,

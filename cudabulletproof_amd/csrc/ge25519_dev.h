@@ -43,7 +43,8 @@ BP_DEV fe k_const() {
 // fe25519_mul(f, k) (the C = (T1 T2) k of every point operation): the same exact 512-bit product and
 // fold as fe_mul(f, k_const()), with the product counting only the carries a column's running-sum
 // bound allows (mul512_k_asm: 16 counts instead of 50; k's words are SGPR operands).
-BP_DEV fe fe_mul_k(const fe& f) {
+template <int LAT = 0>
+BP_DEV fe fe_mul_k(const fe& f, uint32_t* acc = nullptr) {
 #if BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     uint32_t a[8], w[16];
 #pragma unroll
@@ -55,7 +56,7 @@ BP_DEV fe fe_mul_k(const fe& f) {
     uint64_t t[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) t[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-    return fe_fold512(t);
+    return fe_fold512<LAT>(t, acc);   // (the product by k has no gate)
 #else
     return fe_mul(f, k_const());
 #endif
@@ -209,6 +210,97 @@ BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q) {
     return ge{fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
 }
 
+// ---- deferred forms (the lane loops' common pass) ----
+// The point forms above test, inside every field block, for a rare edge of the fix-up (about 2^-32
+// of lanes) and, before every general product and square, the bounded product's gate (about 2^-27):
+// some 22 compares, each with a SALU test and a branch, per point operation, whose results the step
+// can never use.  The forms below run the blocks' fast statements only (fe25519_dev.h LAT 3) and max
+// the words those tests read into two running words: acc reaches 2^32-1 exactly when a block's test
+// would have fired for this lane, gacc exceeds MUL_BOUNDED_WORD exactly when a gate would have.  A max
+// only grows and the first edge is met on operands that are still correct, so one test of the two
+// words is sound wherever it is placed later; on a hit the caller drops the pass and reruns the
+// scalar multiplication from its start with the forms above (scalarmult), so the results are the
+// same bits.  (The row form recomputes one step instead: it can keep the step's inputs live; here the
+// lane forms sit at the VGPR limit.)  fe_mul_one keeps its in-statement test.
+#ifndef BP_LANE_DEFER
+#define BP_LANE_DEFER 1   // 0: scalarmult runs the gated forms only (A/B builds)
+#endif
+#ifndef BP_DEFER_CHUNK
+#define BP_DEFER_CHUNK 32   // loop steps between two tests of the running words
+#endif
+constexpr int DEFER_WARM = 2;   // the per-lane loop's steps that run the gated form first (sm_lane_loop_d)
+struct Defer {
+    uint32_t acc = 0, gacc = 0;
+};
+BP_DEV bool defer_hit(const Defer& d) {
+    return __builtin_amdgcn_ballot_w64((d.acc == 0xFFFFFFFFu) | (d.gacc > MUL_BOUNDED_WORD)) != 0;
+}
+
+BP_DEV void lane_addsub_d(const fe& f, const fe& g, fe& sum, fe& diff, Defer& d) {
+#if BP_LANE_ADDSUB
+    fe_addsub<3>(f, g, sum, diff, &d.acc);
+#else
+    diff = fe_sub<3>(f, g, &d.acc);
+    sum = fe_add<3>(f, g, &d.acc);
+#endif
+}
+
+// ge_dbl, deferred
+BP_DEV ge ge_dbl_d(const ge& p, Defer& d) {
+    fe A = fe_sq<3>(fe_sub<3>(p.Y, p.X, &d.acc), &d.acc, &d.gacc);
+    fe B = fe_sq<3>(fe_add<3>(p.Y, p.X, &d.acc), &d.acc, &d.gacc);
+    fe C = fe_mul_k<3>(fe_sq<3>(p.T, &d.acc, &d.gacc), &d.acc);
+    fe D = fe_sq<3>(p.Z, &d.acc, &d.gacc);
+    D = fe_add<3>(D, D, &d.acc);
+    fe E, F, G, H;
+    lane_addsub_d(B, A, H, E, d);   // H = B + A, E = B - A
+    lane_addsub_d(D, C, G, F, d);   // G = D + C, F = D - C
+    return ge{fe_mul<3>(E, F, &d.acc, &d.gacc), fe_mul<3>(G, H, &d.acc, &d.gacc), fe_mul<3>(F, G, &d.acc, &d.gacc),
+              fe_mul<3>(E, H, &d.acc, &d.gacc)};
+}
+
+// ge_add_qp, deferred
+template <bool QLDS>
+BP_DEV ge ge_add_qp_d(const ge& p, const geq* q, bool zone, Defer& d) {
+    fe A = fe_mul<3>(fe_sub<3>(p.Y, p.X, &d.acc), qget<QLDS>(&q->YmX), &d.acc, &d.gacc);
+    fe B = fe_mul<3>(fe_add<3>(p.Y, p.X, &d.acc), qget<QLDS>(&q->YpX), &d.acc, &d.gacc);
+    fe C = fe_mul_k<3>(fe_mul<3>(p.T, qget<QLDS>(&q->T), &d.acc, &d.gacc), &d.acc);
+    fe D = zone ? fe_mul_one(p.Z) : fe_mul<3>(p.Z, qget<QLDS>(&q->Z), &d.acc, &d.gacc);
+    D = fe_add<3>(D, D, &d.acc);
+    fe E, F, G, H;
+    lane_addsub_d(B, A, H, E, d);   // H = B + A, E = B - A
+    lane_addsub_d(D, C, G, F, d);   // G = D + C, F = D - C
+    return ge{fe_mul<3>(E, F, &d.acc, &d.gacc), fe_mul<3>(G, H, &d.acc, &d.gacc), fe_mul<3>(F, G, &d.acc, &d.gacc),
+              fe_mul<3>(E, H, &d.acc, &d.gacc)};
+}
+
+// ge_add_sel, deferred
+template <bool QLDS, bool ZONE = false>
+BP_DEV ge ge_add_sel_d(const ge& p, const geq* q, bool use_q, Defer& d) {
+    fe ymx = fe_sub<3>(p.Y, p.X, &d.acc);
+    fe qa = qget<QLDS>(&q->YmX);
+    fe A = fe_mul<3>(ymx, use_q ? qa : ymx, &d.acc, &d.gacc);
+    fe ypx = fe_add<3>(p.Y, p.X, &d.acc);
+    fe qb = qget<QLDS>(&q->YpX);
+    fe B = fe_mul<3>(ypx, use_q ? qb : ypx, &d.acc, &d.gacc);
+    fe qt = qget<QLDS>(&q->T);
+    fe C = fe_mul_k<3>(fe_mul<3>(p.T, use_q ? qt : p.T, &d.acc, &d.gacc), &d.acc);
+    fe D;
+    if (ZONE) {
+        fe d1 = fe_mul_one(p.Z), d2 = fe_sq<3>(p.Z, &d.acc, &d.gacc);
+        D = use_q ? d1 : d2;
+    } else {
+        fe qz = qget<QLDS>(&q->Z);
+        D = fe_mul<3>(p.Z, use_q ? qz : p.Z, &d.acc, &d.gacc);
+    }
+    D = fe_add<3>(D, D, &d.acc);
+    fe E, F, G, H;
+    lane_addsub_d(B, A, H, E, d);   // H = B + A, E = B - A
+    lane_addsub_d(D, C, G, F, d);   // G = D + C, F = D - C
+    return ge{fe_mul<3>(E, F, &d.acc, &d.gacc), fe_mul<3>(G, H, &d.acc, &d.gacc), fe_mul<3>(F, G, &d.acc, &d.gacc),
+              fe_mul<3>(E, H, &d.acc, &d.gacc)};
+}
+
 // MSB-first bit stream over a 256-bit scalar, kept as a shift register of limbs so that no
 // array is ever indexed by a run-time value (that would place the scalar in scratch).
 struct BitStream {
@@ -275,6 +367,46 @@ BP_DEV ge sm_uniform(const fe& s_in, const geq* q, const ge* __restrict__ dtab, 
     return r;
 }
 
+// sm_uniform's common pass with the deferred forms: false when some lane met a rare edge or a failed
+// gate (tested every BP_DEFER_CHUNK steps and after the loop; FORCE: after the first chunk whatever the
+// data, the probe's recovery mode), and the caller then runs sm_uniform itself.
+template <bool QLDS, bool FORCE>
+BP_DEV bool sm_uniform_d(ge& out, const fe& s_in, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
+    fe s;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)s_in.v[i]);
+        uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(s_in.v[i] >> 32));
+        s.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    int lz = fe_clz256(s);
+    const bool pre = K > 0 && lz < K && __all(ptab != nullptr);
+    const int top = pre ? 255 - K : 255 - lz;
+    ge r = ld_ge(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
+    if (top >= 0) {
+        const bool zone = __all(fe_is_one(qget<QLDS>(&q->Z)));
+        BitStream bs = bs_init(s, top);
+        // the top bit's step with the gated forms: the start state from dtab is a doubled identity,
+        // whose small coordinates (Y - X with a zero word 1) sit on fe25519_sub's rare edge in every
+        // lane; after the first add of P the state is an ordinary point (DEFER_WARM, below)
+        r = ge_dbl(r);
+        if (bs_next(bs)) r = ge_add_qp<QLDS>(r, q, zone);
+        Defer d;
+        int n = 0;
+        for (int i = top - 1; i >= 0; i--) {
+            r = ge_dbl_d(r, d);
+            if (bs_next(bs)) r = ge_add_qp_d<QLDS>(r, q, zone, d);
+            if (++n == BP_DEFER_CHUNK) {
+                n = 0;
+                if (FORCE || __builtin_expect(defer_hit(d), 0)) return false;
+            }
+        }
+        if (__builtin_expect(defer_hit(d), 0)) return false;
+    }
+    out = r;
+    return true;
+}
+
 // Same function for a per-lane scalar: every iteration is one ge25519_add whose second
 // operand is either r itself (the doubling) or P, so no lane idles on the other's branch.
 template <bool QLDS, bool ZONE>
@@ -299,16 +431,76 @@ BP_DEV ge sm_lane_loop(const fe& s, const geq* q, const ge* __restrict__ dtab, c
     return r;
 }
 
-template <bool QLDS>
+// sm_lane_loop's common pass with the deferred forms (as sm_uniform_d; n counts the wave's steps).
+template <bool QLDS, bool ZONE, bool FORCE>
+BP_DEV bool sm_lane_loop_d(ge& out, const fe& s, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
+    int lz = fe_clz256(s);
+    const bool pre = K > 0 && lz < K && ptab != nullptr;
+    ge r = ld_ge(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
+    int i = pre ? 255 - K : 255 - lz;   // index of the pending bit
+    BitStream bs = bs_init(s, i < 0 ? 0 : i);
+    uint32_t bit = i >= 0 ? bs_next(bs) : 0;
+    bool add_phase = false;
+    // A lane's first DEFER_WARM steps (the top bit's doubling and add) run the gated form: the start
+    // state from dtab is a doubled identity, whose small coordinates put Y - X on fe25519_sub's rare
+    // edge (word 1 of the difference is 0) in every lane, and the deferred pass would be dropped in
+    // every wave.  After the first add of P the state is an ordinary point.
+    for (int warm = 0; warm < DEFER_WARM && i >= 0; warm++) {
+        r = ge_add_sel<QLDS, ZONE>(r, q, add_phase);
+        if (!add_phase && bit) {
+            add_phase = true;
+        } else {
+            add_phase = false;
+            i--;
+            bit = bs_next(bs);
+        }
+    }
+    Defer d;
+    int n = 0;
+    bool hit = false;
+    while (i >= 0) {
+        r = ge_add_sel_d<QLDS, ZONE>(r, q, add_phase, d);
+        if (!add_phase && bit) {
+            add_phase = true;
+        } else {
+            add_phase = false;
+            i--;
+            bit = bs_next(bs);
+        }
+        if (++n == BP_DEFER_CHUNK) {   // n is the same in every lane still in the loop
+            n = 0;
+            if (FORCE || __builtin_expect(defer_hit(d), 0)) {
+                hit = true;
+                break;
+            }
+        }
+    }
+    // lanes that left the loop earlier did not see a later chunk's hit: one vote for the whole wave
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit) != 0 || defer_hit(d), 0)) return false;
+    out = r;
+    return true;
+}
+
+template <bool QLDS, bool FORCE = false>
 BP_DEV ge sm_lane(const fe& s, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
-    if (__all(fe_is_one(qget<QLDS>(&q->Z)))) return sm_lane_loop<QLDS, true>(s, q, dtab, ptab, K);
+    const bool zone = __all(fe_is_one(qget<QLDS>(&q->Z)));
+#if BP_LANE_DEFER
+    ge r;
+    if (zone ? sm_lane_loop_d<QLDS, true, FORCE>(r, s, q, dtab, ptab, K)
+             : sm_lane_loop_d<QLDS, false, FORCE>(r, s, q, dtab, ptab, K))
+        return r;
+#endif
+    if (zone) return sm_lane_loop<QLDS, true>(s, q, dtab, ptab, K);
     return sm_lane_loop<QLDS, false>(s, q, dtab, ptab, K);
 }
 
 // Wave-level dispatch: uniform scalar -> scalar-branch loop, else the per-lane loop.
 // QLDS: `slot` is this lane's LDS slot and receives ge_prep(P); otherwise q stays in VGPRs.
 // ptab / K: this lane's base's prefix table (nullable) and its width in bits (0: none).
-template <bool QLDS>
+// The loops first run their deferred pass (above); when it reports a rare edge or a failed gate in
+// some lane the wave runs the same scalar multiplication again from its start state (s, the slot,
+// dtab, ptab and K are all still there) with the gated forms.  FORCE: see sm_uniform_d.
+template <bool QLDS, bool FORCE = false>
 BP_DEV ge scalarmult(const fe& s, const ge& P, geq* slot, const ge* __restrict__ dtab, const ge* ptab = nullptr,
                      int K = 0) {
     geq qreg;
@@ -333,8 +525,14 @@ BP_DEV ge scalarmult(const fe& s, const ge& P, geq* slot, const ge* __restrict__
         uint32_t lo = (uint32_t)s.v[i], hi = (uint32_t)(s.v[i] >> 32);
         same &= (lo == __builtin_amdgcn_readfirstlane(lo)) & (hi == __builtin_amdgcn_readfirstlane(hi));
     }
-    if (__all(same)) return sm_uniform<QLDS>(s, q, dtab, ptab, K);
-    return sm_lane<QLDS>(s, q, dtab, ptab, K);
+    if (__all(same)) {
+#if BP_LANE_DEFER
+        ge r;
+        if (sm_uniform_d<QLDS, FORCE>(r, s, q, dtab, ptab, K)) return r;
+#endif
+        return sm_uniform<QLDS>(s, q, dtab, ptab, K);
+    }
+    return sm_lane<QLDS, FORCE>(s, q, dtab, ptab, K);
 }
 
 }  // namespace bp

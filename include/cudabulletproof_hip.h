@@ -460,7 +460,9 @@ int hipbp_point_tree(ge25519* result, const ge25519* points, size_t n, void* str
  * 12 the same split over a lane quad (fe_mul_q4_k, four lanes per element); the 16-lane row step's
  * field blocks (same values as ops 0 / 8 / 9 / 6): 13 add, 15 / 16 add-sub, 19 fold in their latency
  * forms, and 14, 17 / 18, 20 the same through their deferred rare-edge test (fast form, recomputed
- * when the element's test words hit 2^32-1). */
+ * when the element's test words hit 2^32-1); the lane loops' deferred forms, each recomputed with
+ * the gated form when the element's running words report an edge or a failed product gate: 21 add,
+ * 22 / 23 add-sub, 24 fold, 25 mul, 26 sq (b unused), 27 sub (same values as ops 0, 8 / 9, 6, 2, 7, 1). */
 int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_t count, void* stream);
 /* The verify path's SHA-256 message shapes on the device, item i over in[6i .. 6i+5] (device
  * pointers): kind 0 the y challenge (points (in0,in1), (in2,in3), (in4,in5) as X, Y), 1 z (in0),
@@ -468,6 +470,11 @@ int hipbp_field_op(int op, fe25519* r, const fe25519* a, const fe25519* b, size_
  * R.X in2), 4 the prover's IPA transcript start (t in0, taux in1, mu in2), 5 the unmasked digest of
  * in0..in3 in raw limb order.  For checking against FIPS 180-4 (bulletproof_challenge.cu:6-77). */
 int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, void* stream);
+/* out[i] = ge25519_scalarmult(scalars[i], points[i]) as the raw extended point, through the call site
+ * every kernel uses (device pointers).  force != 0: the loops' deferred pass reports a hit after its
+ * first chunk of steps whatever the data, so the call takes the recovery path (the rerun with the
+ * gated forms); the results are the same bits either way.  For tests. */
+int hipbp_sm_probe(int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count, void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
  * point-tree, prover, the seeded prover's scalars and keys, the accepted prover's retry workspace, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
  * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;

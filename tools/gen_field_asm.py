@@ -354,7 +354,8 @@ def gen_add(lat=False, acc=False):
     fast += fix_m1(h)
     lf, _ = schedule(fast)
     if acc:
-        return emit_acc("fe_add_asm_lat_acc", ["fe_add_asm_lat's fast statement, the rare-edge test deferred into acc (emit_acc)."],
+        return emit_acc("fe_add_asm" + ("_lat" if lat else "") + "_acc",
+                        ["fe_add_asm" + ("_lat" if lat else "") + "'s fast statement, the rare-edge test deferred into acc (emit_acc)."],
                         [("fa", "a"), ("ga", "b")], h, ["vt1", "vt3"], ["scy"],
                         schedule(to_acc(fast))[0], ADD_POST)
     ls, _ = schedule(add_chain(h) + fix_seq(h, h, "scy"))
@@ -394,7 +395,8 @@ def gen_fold(lat=False, acc=False):
     fast += fix_m1(h)
     lf, _ = schedule(fast)
     if acc:
-        return emit_acc("fe_fold_asm_lat_acc", ["fe_fold_asm_lat's fast statement, the rare-edge test deferred into acc (emit_acc)."],
+        return emit_acc("fe_fold_asm" + ("_lat" if lat else "") + "_acc",
+                        ["fe_fold_asm" + ("_lat" if lat else "") + "'s fast statement, the rare-edge test deferred into acc (emit_acc)."],
                         [("ta", "a"), ("xa", "x")], h, ["vt1", "vt3"], ["scy"],
                         schedule(to_acc(fast))[0], ADD_POST)
     ls, _ = schedule(exact + fix_seq(h, h, "scy"))
@@ -407,7 +409,7 @@ def gen_fold(lat=False, acc=False):
                       FIX_SGPRS + ["scy", "sq1", "sq2", "sq3"], ls, ADD_POST, ["vt1", "vt3"])
 
 
-def gen_sub():
+def gen_sub(acc=False):
     """fe25519_sub (curve25519_ops.cu:71-90): t = f - g with the lossy borrow
     br_i = b_i & !(g_i == 2^64-1 & br_{i-1}); on a final borrow m, the literal "+ p" pass:
     o0 = t0 - 19m; o1 = t1 - (m & t0 < 19); o2 = t2 - (m & o1 == M); o3 = t3 + m 2^63 - (m & o2 == M)
@@ -462,6 +464,9 @@ def gen_sub():
          V("v_max_u32 %[vt3], %[vt3], %[h4]"),
          V("v_cmp_eq_u32 %[srare], -1, %[vt3]", ["srare"])] + plain[5:] + fastp
     lf, _ = schedule(fast)
+    if acc:
+        return emit_acc("fe_sub_asm_acc", ["fe_sub_asm's fast statement, the rare-edge test deferred into acc (emit_acc)."],
+                        [("fa", "a"), ("ga", "b")], t, ["vt1", "vt3"], ["scy"], schedule(to_acc(fast))[0], SUB_POST)
     ls, _ = schedule(exact + exactp)
     return emit_split("fe_sub_asm", ["fe25519_sub (curve25519_ops.cu:71-90) on limb halves: lossy borrow chain, then the",
                                      "literal \"+ p\" pass on a final borrow (fast forms unless a lane is on a rare edge)."],
@@ -542,7 +547,8 @@ def gen_addsub(lat=False, acc=False):
         V("v_add_u32 %[h7], %[h7], %[vt2]")], {**{f"h{i}": f"t{i}" for i in range(8)}, "scy": "sby"})
     lf, _ = schedule(pre + fast)
     if acc:
-        return emit_acc("fe_addsub_asm_lat_acc", ["fe_addsub_asm_lat's fast statement, the rare-edge test deferred into acc (emit_acc)."],
+        return emit_acc("fe_addsub_asm" + ("_lat" if lat else "") + "_acc",
+                        ["fe_addsub_asm" + ("_lat" if lat else "") + "'s fast statement, the rare-edge test deferred into acc (emit_acc)."],
                         [("fa", "a"), ("ga", "b")], h + [f"t{i}" for i in range(8)],
                         ["vt1", "vt3", "vt4"], ["scy", "sby"],
                         schedule(to_acc(pre + fast))[0], ADDSUB_POST)
@@ -644,7 +650,10 @@ def main(path=OUT):
             "// form (fix_m1) these are the blocks above again, kept under the names their callers select by."]
     out += gen_add(lat=True) + [""] + gen_fold(lat=True) + [""] + gen_addsub(lat=True) + [""]
     out += ["// The row step's fast statements with the rare-edge test deferred (emit_acc; ge25519_quad.h sm_row)."]
-    out += gen_add(lat=True, acc=True) + [""] + gen_fold(lat=True, acc=True) + [""] + gen_addsub(lat=True, acc=True)
+    out += gen_add(lat=True, acc=True) + [""] + gen_fold(lat=True, acc=True) + [""] + gen_addsub(lat=True, acc=True) + [""]
+    out += ["// The throughput forms' fast statements with the rare-edge test deferred (emit_acc; ge25519_dev.h: the lane",
+            "// loops' deferred point forms, one test per chunk of steps, a hit reruns the scalar multiplication)."]
+    out += gen_add(acc=True) + [""] + gen_sub(acc=True) + [""] + gen_fold(acc=True) + [""] + gen_addsub(acc=True)
     out.append("}  // namespace bp")
     open(path, "w").write("\n".join(out) + "\n")
     print("wrote", path)
