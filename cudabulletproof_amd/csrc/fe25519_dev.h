@@ -103,26 +103,42 @@ BP_DEV uint64_t mul19(uint64_t x) {
 #endif
 }
 
+BP_DEV uint32_t lo32(uint64_t x) { return (uint32_t)x; }
+BP_DEV uint32_t hi32(uint64_t x) { return (uint32_t)(x >> 32); }
+BP_DEV uint64_t cat64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+
+// A field element as the eight 32-bit words the generated blocks take, and back.
+BP_DEV void fe_words(uint32_t a[8], const fe& f) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        a[2 * i] = lo32(f.v[i]);
+        a[2 * i + 1] = hi32(f.v[i]);
+    }
+}
+// (two operands limb by limb: taking them one after the other changes the order the compiler emits a
+// block's neighbours in, not the bits)
+BP_DEV void fe_words(uint32_t a[8], uint32_t b[8], const fe& f, const fe& g) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        a[2 * i] = lo32(f.v[i]); a[2 * i + 1] = hi32(f.v[i]);
+        b[2 * i] = lo32(g.v[i]); b[2 * i + 1] = hi32(g.v[i]);
+    }
+}
+BP_DEV fe fe_of_words(const uint32_t o[8]) {
+    return fe{{cat64(o[0], o[1]), cat64(o[2], o[3]), cat64(o[4], o[5]), cat64(o[6], o[7])}};
+}
+
 // host fe25519_tobytes (curve25519_ops.cu:220-251) minus the byte store: canonicalising limbs.
 BP_DEV fe fe_canon(const fe& t) {
 #if BP_FIELD_ASM && defined(__HIP_DEVICE_COMPILE__)   // generated gfx950 form (field_asm.h), same bits
     uint32_t a[8], o[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[2 * i] = (uint32_t)t.v[i];
-        a[2 * i + 1] = (uint32_t)(t.v[i] >> 32);
-    }
+    fe_words(a, t);
     fe_canon_asm(o, a);
-    return fe{{(uint64_t)o[0] | ((uint64_t)o[1] << 32), (uint64_t)o[2] | ((uint64_t)o[3] << 32),
-               (uint64_t)o[4] | ((uint64_t)o[5] << 32), (uint64_t)o[6] | ((uint64_t)o[7] << 32)}};
+    return fe_of_words(o);
 #else
     return fe_cond_sub_p(t, fe_ge_p(t));
 #endif
 }
-
-BP_DEV uint32_t lo32(uint64_t x) { return (uint32_t)x; }
-BP_DEV uint32_t hi32(uint64_t x) { return (uint32_t)(x >> 32); }
-BP_DEV uint64_t cat64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
 
 // fe25519_add (curve25519_ops.cu:41-68): exact 257-bit sum (one 32-bit carry chain), then
 // one lossy "- p" when the sum carried out or is >= p.
@@ -134,13 +150,9 @@ template <int LAT = 0>
 BP_DEV fe fe_add(const fe& f, const fe& g, uint32_t* acc = nullptr) {
 #if BP_FIELD_ASM && defined(__HIP_DEVICE_COMPILE__)   // generated gfx950 form (field_asm.h), same bits
     uint32_t a[8], b[8], o[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[2 * i] = lo32(f.v[i]); a[2 * i + 1] = hi32(f.v[i]);
-        b[2 * i] = lo32(g.v[i]); b[2 * i + 1] = hi32(g.v[i]);
-    }
+    fe_words(a, b, f, g);
     if constexpr (LAT == 3) fe_add_asm_acc(o, a, b, *acc); else if constexpr (LAT == 2) fe_add_asm_lat_acc(o, a, b, *acc); else if constexpr (LAT == 1) fe_add_asm_lat(o, a, b); else fe_add_asm(o, a, b);
-    return fe{{cat64(o[0], o[1]), cat64(o[2], o[3]), cat64(o[4], o[5]), cat64(o[6], o[7])}};
+    return fe_of_words(o);
 #else
     fe h;
     unsigned c = 0;
@@ -164,13 +176,9 @@ template <int LAT = 0>
 BP_DEV fe fe_sub(const fe& f, const fe& g, uint32_t* acc = nullptr) {
 #if BP_FIELD_ASM && defined(__HIP_DEVICE_COMPILE__)   // generated gfx950 form (field_asm.h), same bits
     uint32_t a[8], b[8], o[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[2 * i] = lo32(f.v[i]); a[2 * i + 1] = hi32(f.v[i]);
-        b[2 * i] = lo32(g.v[i]); b[2 * i + 1] = hi32(g.v[i]);
-    }
+    fe_words(a, b, f, g);
     if constexpr (LAT == 3) fe_sub_asm_acc(o, a, b, *acc); else fe_sub_asm(o, a, b);
-    return fe{{cat64(o[0], o[1]), cat64(o[2], o[3]), cat64(o[4], o[5]), cat64(o[6], o[7])}};
+    return fe_of_words(o);
 #else
     fe t;
     unsigned br = 0;
@@ -201,17 +209,13 @@ template <int LAT = 0>
 BP_DEV void fe_addsub(const fe& f, const fe& g, fe& sum, fe& diff, uint32_t* acc = nullptr) {
 #if BP_FIELD_ASM && defined(__HIP_DEVICE_COMPILE__)
     uint32_t a[8], b[8], os[8], od[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[2 * i] = lo32(f.v[i]); a[2 * i + 1] = hi32(f.v[i]);
-        b[2 * i] = lo32(g.v[i]); b[2 * i + 1] = hi32(g.v[i]);
-    }
+    fe_words(a, b, f, g);
     if constexpr (LAT == 3) fe_addsub_asm_acc(os, od, a, b, *acc);
     else if constexpr (LAT == 2) fe_addsub_asm_lat_acc(os, od, a, b, *acc);
     else if constexpr (LAT == 1) fe_addsub_asm_lat(os, od, a, b);
     else fe_addsub_asm(os, od, a, b);
-    sum = fe{{cat64(os[0], os[1]), cat64(os[2], os[3]), cat64(os[4], os[5]), cat64(os[6], os[7])}};
-    diff = fe{{cat64(od[0], od[1]), cat64(od[2], od[3]), cat64(od[4], od[5]), cat64(od[6], od[7])}};
+    sum = fe_of_words(os);
+    diff = fe_of_words(od);
 #else
     sum = fe_add(f, g);
     diff = fe_sub(f, g);
@@ -235,7 +239,7 @@ BP_DEV fe fe_fold512(const uint64_t t[8], uint32_t* acc = nullptr) {
         xh[2 * i] = lo32(x); xh[2 * i + 1] = hi32(x);
     }
     if constexpr (LAT == 3) fe_fold_asm_acc(o, a, xh, *acc); else if constexpr (LAT == 2) fe_fold_asm_lat_acc(o, a, xh, *acc); else if constexpr (LAT == 1) fe_fold_asm_lat(o, a, xh); else fe_fold_asm(o, a, xh);
-    return fe{{cat64(o[0], o[1]), cat64(o[2], o[3]), cat64(o[4], o[5]), cat64(o[6], o[7])}};
+    return fe_of_words(o);
 #else
     fe h;
     unsigned cy = 0;
@@ -271,13 +275,7 @@ BP_DEV void mul_gate_defer(uint32_t& gacc, uint32_t x, uint32_t y) {
 template <bool DEFER = false>
 BP_DEV void mul512(uint64_t t[8], const fe& f, const fe& g, uint32_t* gacc = nullptr) {
     uint32_t a[8], b[8], w[16];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[2 * i] = (uint32_t)f.v[i];
-        a[2 * i + 1] = (uint32_t)(f.v[i] >> 32);
-        b[2 * i] = (uint32_t)g.v[i];
-        b[2 * i + 1] = (uint32_t)(g.v[i] >> 32);
-    }
+    fe_words(a, b, f, g);
 #if BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)   // host pass: the C form (host-side checks)
     // bounded form (the first carry of every column uncounted, mul512_asm.h) unless a lane's gating
     // words a[0], b[7] exceed MUL_BOUNDED_WORD (a wave-uniform test; ~2^-27 per lane): then the
@@ -308,7 +306,7 @@ BP_DEV void mul512(uint64_t t[8], const fe& f, const fe& g, uint32_t* gacc = nul
     w[15] = (uint32_t)acc;
 #endif
 #pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    for (int i = 0; i < 8; i++) t[i] = cat64(w[2 * i], w[2 * i + 1]);
 }
 
 // fe25519_mul (curve25519_ops.cu:93-146 == device_curve25519_ops.cuh:117-171)
@@ -329,11 +327,7 @@ BP_DEV fe fe_mul(const fe& f, const fe& g, uint32_t* acc = nullptr, uint32_t* ga
 template <bool DEFER = false>
 BP_DEV void sqr512(uint64_t t[8], const fe& f, uint32_t* gacc = nullptr) {
     uint32_t a[8], o[16], w[16];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[2 * i] = (uint32_t)f.v[i];
-        a[2 * i + 1] = (uint32_t)(f.v[i] >> 32);
-    }
+    fe_words(a, f);
 #if BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     sqr512_offdiag_bounded_asm(o, a);
     if constexpr (DEFER) mul_gate_defer(*gacc, a[0], a[7]);
@@ -373,7 +367,7 @@ BP_DEV void sqr512(uint64_t t[8], const fe& f, uint32_t* gacc = nullptr) {
         w[2 * i + 1] = __builtin_addc(hi, (uint32_t)(di >> 32), c, &c);
     }
 #pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    for (int i = 0; i < 8; i++) t[i] = cat64(w[2 * i], w[2 * i + 1]);
 }
 
 // fe25519_sq (curve25519_ops.cu:149) == mul(f, f): the same exact product, then the same fold.

@@ -12,20 +12,6 @@
 
 namespace bp {
 
-#ifndef BP_LANE_ADDSUB
-#define BP_LANE_ADDSUB 1
-#endif
-// E/H and F/G of ge25519_add: one fused block (fe_addsub, chains interleaved) or two calls
-// (-DBP_LANE_ADDSUB=0, for A/B builds); the same bits either way.
-BP_DEV void lane_addsub(const fe& f, const fe& g, fe& sum, fe& diff) {
-#if BP_LANE_ADDSUB
-    fe_addsub(f, g, sum, diff);
-#else
-    diff = fe_sub(f, g);
-    sum = fe_add(f, g);
-#endif
-}
-
 struct ge {
     fe X, Y, Z, T;
 };
@@ -47,15 +33,11 @@ template <int LAT = 0>
 BP_DEV fe fe_mul_k(const fe& f, uint32_t* acc = nullptr) {
 #if BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     uint32_t a[8], w[16];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[2 * i] = (uint32_t)f.v[i];
-        a[2 * i + 1] = (uint32_t)(f.v[i] >> 32);
-    }
+    fe_words(a, f);
     mul512_k_asm(w, a);
     uint64_t t[8];
 #pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    for (int i = 0; i < 8; i++) t[i] = cat64(w[2 * i], w[2 * i + 1]);
     return fe_fold512<LAT>(t, acc);   // (the product by k has no gate)
 #else
     return fe_mul(f, k_const());
@@ -66,34 +48,6 @@ BP_DEV ge ge_zero() { return ge{fe_set(0), fe_set(1), fe_set(1), fe_set(0)}; }  
 
 BP_DEV geq ge_prep(const ge& q) {
     return geq{fe_sub(q.Y, q.X), fe_add(q.Y, q.X), q.Z, q.T};
-}
-
-// ge25519_add (curve25519_ops.cu:326-378 == device_curve25519_ops.cuh:188-241)
-BP_DEV ge ge_add_q(const ge& p, const geq& q) {
-    fe A = fe_mul(fe_sub(p.Y, p.X), q.YmX);
-    fe B = fe_mul(fe_add(p.Y, p.X), q.YpX);
-    fe C = fe_mul_k(fe_mul(p.T, q.T));
-    fe D = fe_mul(p.Z, q.Z);
-    D = fe_add(D, D);
-    fe E, F, G, H;
-    lane_addsub(B, A, H, E);   // H = B + A, E = B - A
-    lane_addsub(D, C, G, F);   // G = D + C, F = D - C
-    return ge{fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
-}
-
-BP_DEV ge ge_add(const ge& p, const ge& q) { return ge_add_q(p, ge_prep(q)); }
-
-// add(p, p) (curve25519_ops.cu:406 / device .cuh:282)
-BP_DEV ge ge_dbl(const ge& p) {
-    fe A = fe_sq(fe_sub(p.Y, p.X));
-    fe B = fe_sq(fe_add(p.Y, p.X));
-    fe C = fe_mul_k(fe_sq(p.T));
-    fe D = fe_sq(p.Z);
-    D = fe_add(D, D);
-    fe E, F, G, H;
-    lane_addsub(B, A, H, E);   // H = B + A, E = B - A
-    lane_addsub(D, C, G, F);   // G = D + C, F = D - C
-    return ge{fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
 }
 
 // device_ge25519_normalize (device_curve25519_ops.cuh:243-270): z_inv = 1.
@@ -161,20 +115,87 @@ BP_DEV fe qget(const fe* p) {
     return *p;
 }
 
-// ge25519_add(p, q) with q's prepared operands (same operation order as ge_add_q).
+// ---- the field mode of a point form ----
+// Every point form below is written once and takes a mode, which says how its field blocks treat
+// their two rare tests: the fix-up's rare edge inside every block (about 2^-32 of lanes) and the
+// bounded product's gate before every general product and square (about 2^-27), some 22 compares,
+// each with a SALU test and a branch, per point operation, whose results the step can never use.
+//  * Gated: every block tests in place and takes its exact form on a hit (fe25519_dev.h LAT 0).
+//  * Defer: the blocks run their fast statements only (LAT 3) and max the words those tests read
+//    into the mode's two running words: acc reaches 2^32-1 exactly when a block's test would have
+//    fired for this lane, gacc exceeds MUL_BOUNDED_WORD exactly when a gate would have.  A max only
+//    grows and the first edge is met on operands that are still correct, so one test of the two
+//    words (defer_hit) is sound wherever it is placed later; on a hit the caller drops the pass and
+//    reruns the scalar multiplication from its start in the gated mode (scalarmult), so the results
+//    are the same bits.  (The row form recomputes one step instead: it can keep the step's inputs
+//    live; here the lane forms sit at the VGPR limit.)
+// fe_mul_one keeps its in-statement test in both modes.
+struct Gated {
+    static constexpr int LAT = 0;
+    BP_DEV uint32_t* edge() { return nullptr; }
+    BP_DEV uint32_t* gate() { return nullptr; }
+};
+struct Defer {
+    static constexpr int LAT = 3;
+    uint32_t acc = 0, gacc = 0;
+    BP_DEV uint32_t* edge() { return &acc; }
+    BP_DEV uint32_t* gate() { return &gacc; }
+};
+BP_DEV bool defer_hit(const Gated&) { return false; }
+BP_DEV bool defer_hit(const Defer& d) {
+    return __builtin_amdgcn_ballot_w64((d.acc == 0xFFFFFFFFu) | (d.gacc > MUL_BOUNDED_WORD)) != 0;
+}
+template <class M> BP_DEV fe m_add(const fe& f, const fe& g, M& m) { return fe_add<M::LAT>(f, g, m.edge()); }
+template <class M> BP_DEV fe m_sub(const fe& f, const fe& g, M& m) { return fe_sub<M::LAT>(f, g, m.edge()); }
+template <class M> BP_DEV fe m_mul(const fe& f, const fe& g, M& m) { return fe_mul<M::LAT>(f, g, m.edge(), m.gate()); }
+template <class M> BP_DEV fe m_sq(const fe& f, M& m) { return fe_sq<M::LAT>(f, m.edge(), m.gate()); }
+template <class M> BP_DEV fe m_mul_k(const fe& f, M& m) { return fe_mul_k<M::LAT>(f, m.edge()); }
+#ifndef BP_LANE_ADDSUB
+#define BP_LANE_ADDSUB 1
+#endif
+// E/H and F/G of ge25519_add: one fused block (fe_addsub, chains interleaved) or two calls
+// (-DBP_LANE_ADDSUB=0, for A/B builds); the same bits either way.
+template <class M> BP_DEV void m_addsub(const fe& f, const fe& g, fe& sum, fe& diff, M& m) {
+#if BP_LANE_ADDSUB
+    fe_addsub<M::LAT>(f, g, sum, diff, m.edge());
+#else
+    diff = fe_sub<M::LAT>(f, g, m.edge());
+    sum = fe_add<M::LAT>(f, g, m.edge());
+#endif
+}
+
+// ---- ge25519_add (curve25519_ops.cu:326-378 == device_curve25519_ops.cuh:188-241) ----
+// Stage 1 is A = (Y1-X1)(Y2-X2), B = (Y1+X1)(Y2+X2), C = (T1 T2) k and ZZ = Z1 Z2, in that order; the
+// three shapes below differ only there.  ge_tail is stages 2 and 3, the same for all of them.
+template <class M>
+BP_DEV ge ge_tail(const fe& A, const fe& B, const fe& C, const fe& ZZ, M& m) {
+    fe D = m_add(ZZ, ZZ, m);
+    fe E, F, G, H;
+    m_addsub(B, A, H, E, m);   // H = B + A, E = B - A
+    m_addsub(D, C, G, F, m);   // G = D + C, F = D - C
+    return ge{m_mul(E, F, m), m_mul(G, H, m), m_mul(F, G, m), m_mul(E, H, m)};
+}
+
+// add(p, p) (curve25519_ops.cu:406 / device .cuh:282): the same exact products as squares.
+template <class M>
+BP_DEV ge ge_dbl(const ge& p, M& m) {
+    fe A = m_sq(m_sub(p.Y, p.X, m), m);
+    fe B = m_sq(m_add(p.Y, p.X, m), m);
+    fe C = m_mul_k(m_sq(p.T, m), m);
+    fe ZZ = m_sq(p.Z, m);
+    return ge_tail(A, B, C, ZZ, m);
+}
+
+// add(p, q) with q's prepared operands.
 // zone (wave-uniform): every lane's q.Z is exactly 1 (generators, host-normalized points), so
 // Z1*Z2 = fold(Z1 || 0) = the conditional lossy "- p" of Z1 (fe_mul_one) — same bits, no product.
-template <bool QLDS>
-BP_DEV ge ge_add_qp(const ge& p, const geq* q, bool zone = false) {
-    fe A = fe_mul(fe_sub(p.Y, p.X), qget<QLDS>(&q->YmX));
-    fe B = fe_mul(fe_add(p.Y, p.X), qget<QLDS>(&q->YpX));
-    fe C = fe_mul_k(fe_mul(p.T, qget<QLDS>(&q->T)));
-    fe D = zone ? fe_mul_one(p.Z) : fe_mul(p.Z, qget<QLDS>(&q->Z));
-    D = fe_add(D, D);
-    fe E, F, G, H;
-    lane_addsub(B, A, H, E);   // H = B + A, E = B - A
-    lane_addsub(D, C, G, F);   // G = D + C, F = D - C
-    return ge{fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
+template <bool QLDS, class M>
+BP_DEV ge ge_add_qp(const ge& p, const geq* q, bool zone, M& m) {
+    fe A = m_mul(m_sub(p.Y, p.X, m), qget<QLDS>(&q->YmX), m);
+    fe B = m_mul(m_add(p.Y, p.X, m), qget<QLDS>(&q->YpX), m);
+    fe C = m_mul_k(m_mul(p.T, qget<QLDS>(&q->T), m), m);
+    fe ZZ = zone ? fe_mul_one(p.Z) : m_mul(p.Z, qget<QLDS>(&q->Z), m);
+    return ge_tail(A, B, C, ZZ, m);
 }
 
 // One step of the per-lane loop: add(r, r) when !use_q, add(r, q) when use_q; the
@@ -182,124 +203,46 @@ BP_DEV ge ge_add_qp(const ge& p, const geq* q, bool zone = false) {
 // ZONE (wave-uniform): every lane's q.Z is exactly 1, so the add lanes' Z1*Z2 is fe_mul_one(Z1)
 // and the doubling lanes' is the square Z1^2 — both formed, one kept (the same bits as the
 // general product; 150 + ~20 VALU instead of 189 + the operand select).
-template <bool QLDS, bool ZONE = false>
-BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q) {
+template <bool QLDS, bool ZONE = false, class M>
+BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q, M& m) {
     // q's operands are loaded unconditionally and selected as values: a select between a
     // loaded and a computed value is otherwise folded into a load through a select of
     // pointers, which forces `p` into private memory (scratch).
-    fe ymx = fe_sub(p.Y, p.X);
+    fe ymx = m_sub(p.Y, p.X, m);
     fe qa = qget<QLDS>(&q->YmX);
-    fe A = fe_mul(ymx, use_q ? qa : ymx);
-    fe ypx = fe_add(p.Y, p.X);
+    fe A = m_mul(ymx, use_q ? qa : ymx, m);
+    fe ypx = m_add(p.Y, p.X, m);
     fe qb = qget<QLDS>(&q->YpX);
-    fe B = fe_mul(ypx, use_q ? qb : ypx);
+    fe B = m_mul(ypx, use_q ? qb : ypx, m);
     fe qt = qget<QLDS>(&q->T);
-    fe C = fe_mul_k(fe_mul(p.T, use_q ? qt : p.T));
-    fe D;
+    fe C = m_mul_k(m_mul(p.T, use_q ? qt : p.T, m), m);
+    fe ZZ;
     if (ZONE) {
-        fe d1 = fe_mul_one(p.Z), d2 = fe_sq(p.Z);
-        D = use_q ? d1 : d2;
+        fe d1 = fe_mul_one(p.Z), d2 = m_sq(p.Z, m);
+        ZZ = use_q ? d1 : d2;
     } else {
         fe qz = qget<QLDS>(&q->Z);
-        D = fe_mul(p.Z, use_q ? qz : p.Z);
+        ZZ = m_mul(p.Z, use_q ? qz : p.Z, m);
     }
-    D = fe_add(D, D);
-    fe E, F, G, H;
-    lane_addsub(B, A, H, E);   // H = B + A, E = B - A
-    lane_addsub(D, C, G, F);   // G = D + C, F = D - C
-    return ge{fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
+    return ge_tail(A, B, C, ZZ, m);
 }
 
-// ---- deferred forms (the lane loops' common pass) ----
-// The point forms above test, inside every field block, for a rare edge of the fix-up (about 2^-32
-// of lanes) and, before every general product and square, the bounded product's gate (about 2^-27):
-// some 22 compares, each with a SALU test and a branch, per point operation, whose results the step
-// can never use.  The forms below run the blocks' fast statements only (fe25519_dev.h LAT 3) and max
-// the words those tests read into two running words: acc reaches 2^32-1 exactly when a block's test
-// would have fired for this lane, gacc exceeds MUL_BOUNDED_WORD exactly when a gate would have.  A max
-// only grows and the first edge is met on operands that are still correct, so one test of the two
-// words is sound wherever it is placed later; on a hit the caller drops the pass and reruns the
-// scalar multiplication from its start with the forms above (scalarmult), so the results are the
-// same bits.  (The row form recomputes one step instead: it can keep the step's inputs live; here the
-// lane forms sit at the VGPR limit.)  fe_mul_one keeps its in-statement test.
+// The gated mode under the plain names (every caller outside the lane loops' deferred pass).
+BP_DEV ge ge_dbl(const ge& p) { Gated m; return ge_dbl(p, m); }
+template <bool QLDS>
+BP_DEV ge ge_add_qp(const ge& p, const geq* q, bool zone = false) { Gated m; return ge_add_qp<QLDS>(p, q, zone, m); }
+template <bool QLDS, bool ZONE = false>
+BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q) { Gated m; return ge_add_sel<QLDS, ZONE>(p, q, use_q, m); }
+BP_DEV ge ge_add_q(const ge& p, const geq& q) { return ge_add_qp<false>(p, &q); }
+BP_DEV ge ge_add(const ge& p, const ge& q) { return ge_add_q(p, ge_prep(q)); }
+
 #ifndef BP_LANE_DEFER
-#define BP_LANE_DEFER 1   // 0: scalarmult runs the gated forms only (A/B builds)
+#define BP_LANE_DEFER 1   // 0: scalarmult runs the gated mode only (A/B builds)
 #endif
 #ifndef BP_DEFER_CHUNK
 #define BP_DEFER_CHUNK 32   // loop steps between two tests of the running words
 #endif
-constexpr int DEFER_WARM = 2;   // the per-lane loop's steps that run the gated form first (sm_lane_loop_d)
-struct Defer {
-    uint32_t acc = 0, gacc = 0;
-};
-BP_DEV bool defer_hit(const Defer& d) {
-    return __builtin_amdgcn_ballot_w64((d.acc == 0xFFFFFFFFu) | (d.gacc > MUL_BOUNDED_WORD)) != 0;
-}
-
-BP_DEV void lane_addsub_d(const fe& f, const fe& g, fe& sum, fe& diff, Defer& d) {
-#if BP_LANE_ADDSUB
-    fe_addsub<3>(f, g, sum, diff, &d.acc);
-#else
-    diff = fe_sub<3>(f, g, &d.acc);
-    sum = fe_add<3>(f, g, &d.acc);
-#endif
-}
-
-// ge_dbl, deferred
-BP_DEV ge ge_dbl_d(const ge& p, Defer& d) {
-    fe A = fe_sq<3>(fe_sub<3>(p.Y, p.X, &d.acc), &d.acc, &d.gacc);
-    fe B = fe_sq<3>(fe_add<3>(p.Y, p.X, &d.acc), &d.acc, &d.gacc);
-    fe C = fe_mul_k<3>(fe_sq<3>(p.T, &d.acc, &d.gacc), &d.acc);
-    fe D = fe_sq<3>(p.Z, &d.acc, &d.gacc);
-    D = fe_add<3>(D, D, &d.acc);
-    fe E, F, G, H;
-    lane_addsub_d(B, A, H, E, d);   // H = B + A, E = B - A
-    lane_addsub_d(D, C, G, F, d);   // G = D + C, F = D - C
-    return ge{fe_mul<3>(E, F, &d.acc, &d.gacc), fe_mul<3>(G, H, &d.acc, &d.gacc), fe_mul<3>(F, G, &d.acc, &d.gacc),
-              fe_mul<3>(E, H, &d.acc, &d.gacc)};
-}
-
-// ge_add_qp, deferred
-template <bool QLDS>
-BP_DEV ge ge_add_qp_d(const ge& p, const geq* q, bool zone, Defer& d) {
-    fe A = fe_mul<3>(fe_sub<3>(p.Y, p.X, &d.acc), qget<QLDS>(&q->YmX), &d.acc, &d.gacc);
-    fe B = fe_mul<3>(fe_add<3>(p.Y, p.X, &d.acc), qget<QLDS>(&q->YpX), &d.acc, &d.gacc);
-    fe C = fe_mul_k<3>(fe_mul<3>(p.T, qget<QLDS>(&q->T), &d.acc, &d.gacc), &d.acc);
-    fe D = zone ? fe_mul_one(p.Z) : fe_mul<3>(p.Z, qget<QLDS>(&q->Z), &d.acc, &d.gacc);
-    D = fe_add<3>(D, D, &d.acc);
-    fe E, F, G, H;
-    lane_addsub_d(B, A, H, E, d);   // H = B + A, E = B - A
-    lane_addsub_d(D, C, G, F, d);   // G = D + C, F = D - C
-    return ge{fe_mul<3>(E, F, &d.acc, &d.gacc), fe_mul<3>(G, H, &d.acc, &d.gacc), fe_mul<3>(F, G, &d.acc, &d.gacc),
-              fe_mul<3>(E, H, &d.acc, &d.gacc)};
-}
-
-// ge_add_sel, deferred
-template <bool QLDS, bool ZONE = false>
-BP_DEV ge ge_add_sel_d(const ge& p, const geq* q, bool use_q, Defer& d) {
-    fe ymx = fe_sub<3>(p.Y, p.X, &d.acc);
-    fe qa = qget<QLDS>(&q->YmX);
-    fe A = fe_mul<3>(ymx, use_q ? qa : ymx, &d.acc, &d.gacc);
-    fe ypx = fe_add<3>(p.Y, p.X, &d.acc);
-    fe qb = qget<QLDS>(&q->YpX);
-    fe B = fe_mul<3>(ypx, use_q ? qb : ypx, &d.acc, &d.gacc);
-    fe qt = qget<QLDS>(&q->T);
-    fe C = fe_mul_k<3>(fe_mul<3>(p.T, use_q ? qt : p.T, &d.acc, &d.gacc), &d.acc);
-    fe D;
-    if (ZONE) {
-        fe d1 = fe_mul_one(p.Z), d2 = fe_sq<3>(p.Z, &d.acc, &d.gacc);
-        D = use_q ? d1 : d2;
-    } else {
-        fe qz = qget<QLDS>(&q->Z);
-        D = fe_mul<3>(p.Z, use_q ? qz : p.Z, &d.acc, &d.gacc);
-    }
-    D = fe_add<3>(D, D, &d.acc);
-    fe E, F, G, H;
-    lane_addsub_d(B, A, H, E, d);   // H = B + A, E = B - A
-    lane_addsub_d(D, C, G, F, d);   // G = D + C, F = D - C
-    return ge{fe_mul<3>(E, F, &d.acc, &d.gacc), fe_mul<3>(G, H, &d.acc, &d.gacc), fe_mul<3>(F, G, &d.acc, &d.gacc),
-              fe_mul<3>(E, H, &d.acc, &d.gacc)};
-}
+constexpr int DEFER_WARM = 2;   // the per-lane loop's steps that run gated before its deferred pass (sm_lane_loop)
 
 // MSB-first bit stream over a 256-bit scalar, kept as a shift register of limbs so that no
 // array is ever indexed by a run-time value (that would place the scalar in scratch).
@@ -339,12 +282,31 @@ BP_DEV uint32_t bs_next(BitStream& b) {
     return bit;
 }
 
+// The start of every scalar-multiplication loop: the state after the scalar's leading zeros (dtab) or
+// after its top K bits (the base's prefix table, when it has one and the scalar has fewer than K
+// leading zeros), and in i the index of the pending bit (-1: none, the state is the result).
+// WAVE: the prefix start only when every lane has a table (the start bit must stay wave-uniform).
+template <bool WAVE = false>
+BP_DEV ge sm_start(const fe& s, const ge* ptab, int K, const ge* __restrict__ dtab, int& i) {
+    const int lz = fe_clz256(s);
+    const bool pre = K > 0 && lz < K && (WAVE ? __all(ptab != nullptr) : ptab != nullptr);
+    const ge r = ld_ge(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
+    i = pre ? 255 - K : 255 - lz;
+    return r;
+}
+
 // ge25519_scalarmult (curve25519_ops.cu:397-415 == device .cuh:272-290) for a scalar
 // that is the same in every lane of the wave: the bit test is a scalar branch.
 // `s` holds the scalar's 256 bits (limb i = bytes 8i..8i+7, little-endian); `q` holds
 // ge_prep(P); `dtab` = the identity-doubling table (257 points).
-template <bool QLDS>
-BP_DEV ge sm_uniform(const fe& s_in, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
+// DEFER = true is the common pass in the Defer mode: false when some lane met a rare edge or a failed gate
+// (tested every BP_DEFER_CHUNK steps and once after the loop; FORCE: after the first chunk whatever the
+// data, the probe's recovery mode); DEFER = false is the Gated mode throughout and returns true.  The first
+// steps of a deferred pass run gated: the start state from dtab is a doubled identity, whose small
+// coordinates put Y - X on fe25519_sub's rare edge (word 1 of the difference is 0) in every lane, and the
+// pass would be dropped in every wave; after the first add of P the state is an ordinary point.
+template <bool QLDS, bool DEFER, bool FORCE = false>
+BP_DEV bool sm_uniform(ge& out, const fe& s_in, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
     fe s;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -352,131 +314,82 @@ BP_DEV ge sm_uniform(const fe& s_in, const geq* q, const ge* __restrict__ dtab, 
         uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(s_in.v[i] >> 32));
         s.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
     }
-    int lz = fe_clz256(s);
-    // the prefix start only when every lane has a table (the start bit must stay wave-uniform)
-    const bool pre = K > 0 && lz < K && __all(ptab != nullptr);
-    const int top = pre ? 255 - K : 255 - lz;
-    ge r = ld_ge(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
-    if (top < 0) return r;
-    const bool zone = __all(fe_is_one(qget<QLDS>(&q->Z)));
-    BitStream bs = bs_init(s, top);
-    for (int i = top; i >= 0; i--) {
-        r = ge_dbl(r);
-        if (bs_next(bs)) r = ge_add_qp<QLDS>(r, q, zone);
-    }
-    return r;
-}
-
-// sm_uniform's common pass with the deferred forms: false when some lane met a rare edge or a failed
-// gate (tested every BP_DEFER_CHUNK steps and after the loop; FORCE: after the first chunk whatever the
-// data, the probe's recovery mode), and the caller then runs sm_uniform itself.
-template <bool QLDS, bool FORCE>
-BP_DEV bool sm_uniform_d(ge& out, const fe& s_in, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
-    fe s;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)s_in.v[i]);
-        uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(s_in.v[i] >> 32));
-        s.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    int lz = fe_clz256(s);
-    const bool pre = K > 0 && lz < K && __all(ptab != nullptr);
-    const int top = pre ? 255 - K : 255 - lz;
-    ge r = ld_ge(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
-    if (top >= 0) {
+    int i;
+    ge r = sm_start<true>(s, ptab, K, dtab, i);
+    if (i >= 0) {
         const bool zone = __all(fe_is_one(qget<QLDS>(&q->Z)));
-        BitStream bs = bs_init(s, top);
-        // the top bit's step with the gated forms: the start state from dtab is a doubled identity,
-        // whose small coordinates (Y - X with a zero word 1) sit on fe25519_sub's rare edge in every
-        // lane; after the first add of P the state is an ordinary point (DEFER_WARM, below)
-        r = ge_dbl(r);
-        if (bs_next(bs)) r = ge_add_qp<QLDS>(r, q, zone);
-        Defer d;
+        BitStream bs = bs_init(s, i);
+        if (DEFER) {   // the top bit's step, gated (above)
+            r = ge_dbl(r);
+            if (bs_next(bs)) r = ge_add_qp<QLDS>(r, q, zone);
+            i--;
+        }
+        std::conditional_t<DEFER, Defer, Gated> m;
         int n = 0;
-        for (int i = top - 1; i >= 0; i--) {
-            r = ge_dbl_d(r, d);
-            if (bs_next(bs)) r = ge_add_qp_d<QLDS>(r, q, zone, d);
-            if (++n == BP_DEFER_CHUNK) {
+        for (; i >= 0; i--) {
+            r = ge_dbl(r, m);
+            if (bs_next(bs)) r = ge_add_qp<QLDS>(r, q, zone, m);
+            if (DEFER && ++n == BP_DEFER_CHUNK) {
                 n = 0;
-                if (FORCE || __builtin_expect(defer_hit(d), 0)) return false;
+                if (FORCE || __builtin_expect(defer_hit(m), 0)) return false;
             }
         }
-        if (__builtin_expect(defer_hit(d), 0)) return false;
+        if (DEFER && __builtin_expect(defer_hit(m), 0)) return false;
     }
     out = r;
     return true;
 }
 
+// The per-lane loops' bit bookkeeping after one operation: a doubling at a set bit is followed by the
+// add of P, anything else by the next bit's doubling.
+BP_DEV void lane_advance(bool& add_phase, uint32_t& bit, int& i, BitStream& bs) {
+    if (!add_phase && bit) {
+        add_phase = true;
+    } else {
+        add_phase = false;
+        i--;
+        bit = bs_next(bs);
+    }
+}
+
 // Same function for a per-lane scalar: every iteration is one ge25519_add whose second
 // operand is either r itself (the doubling) or P, so no lane idles on the other's branch.
-template <bool QLDS, bool ZONE>
-BP_DEV ge sm_lane_loop(const fe& s, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
-    int lz = fe_clz256(s);
-    const bool pre = K > 0 && lz < K && ptab != nullptr;
-    ge r = ld_ge(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
-    int i = pre ? 255 - K : 255 - lz;   // index of the pending bit
+template <bool QLDS, bool ZONE, bool DEFER, bool FORCE = false>
+BP_DEV bool sm_lane_loop(ge& out, const fe& s, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
+    int i;   // index of the pending bit
+    ge r = sm_start<false>(s, ptab, K, dtab, i);
     BitStream bs = bs_init(s, i < 0 ? 0 : i);
     uint32_t bit = i >= 0 ? bs_next(bs) : 0;
     bool add_phase = false;    // false: next op doubles; true: next op adds P
-    while (i >= 0) {
+    // a lane's first DEFER_WARM steps (the top bit's doubling and add), gated (above sm_uniform)
+    for (int warm = 0; DEFER && warm < DEFER_WARM && i >= 0; warm++) {
         r = ge_add_sel<QLDS, ZONE>(r, q, add_phase);
-        if (!add_phase && bit) {
-            add_phase = true;
-        } else {
-            add_phase = false;
-            i--;
-            bit = bs_next(bs);
-        }
+        lane_advance(add_phase, bit, i, bs);
     }
-    return r;
-}
-
-// sm_lane_loop's common pass with the deferred forms (as sm_uniform_d; n counts the wave's steps).
-template <bool QLDS, bool ZONE, bool FORCE>
-BP_DEV bool sm_lane_loop_d(ge& out, const fe& s, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
-    int lz = fe_clz256(s);
-    const bool pre = K > 0 && lz < K && ptab != nullptr;
-    ge r = ld_ge(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
-    int i = pre ? 255 - K : 255 - lz;   // index of the pending bit
-    BitStream bs = bs_init(s, i < 0 ? 0 : i);
-    uint32_t bit = i >= 0 ? bs_next(bs) : 0;
-    bool add_phase = false;
-    // A lane's first DEFER_WARM steps (the top bit's doubling and add) run the gated form: the start
-    // state from dtab is a doubled identity, whose small coordinates put Y - X on fe25519_sub's rare
-    // edge (word 1 of the difference is 0) in every lane, and the deferred pass would be dropped in
-    // every wave.  After the first add of P the state is an ordinary point.
-    for (int warm = 0; warm < DEFER_WARM && i >= 0; warm++) {
-        r = ge_add_sel<QLDS, ZONE>(r, q, add_phase);
-        if (!add_phase && bit) {
-            add_phase = true;
-        } else {
-            add_phase = false;
-            i--;
-            bit = bs_next(bs);
+    if constexpr (!DEFER) {
+        while (i >= 0) {
+            r = ge_add_sel<QLDS, ZONE>(r, q, add_phase);
+            lane_advance(add_phase, bit, i, bs);
         }
+        out = r;
+        return true;
     }
-    Defer d;
+    std::conditional_t<DEFER, Defer, Gated> m;
     int n = 0;
     bool hit = false;
     while (i >= 0) {
-        r = ge_add_sel_d<QLDS, ZONE>(r, q, add_phase, d);
-        if (!add_phase && bit) {
-            add_phase = true;
-        } else {
-            add_phase = false;
-            i--;
-            bit = bs_next(bs);
-        }
-        if (++n == BP_DEFER_CHUNK) {   // n is the same in every lane still in the loop
+        r = ge_add_sel<QLDS, ZONE>(r, q, add_phase, m);
+        lane_advance(add_phase, bit, i, bs);
+        if (DEFER && ++n == BP_DEFER_CHUNK) {   // n is the same in every lane still in the loop
             n = 0;
-            if (FORCE || __builtin_expect(defer_hit(d), 0)) {
+            if (FORCE || __builtin_expect(defer_hit(m), 0)) {
                 hit = true;
                 break;
             }
         }
     }
     // lanes that left the loop earlier did not see a later chunk's hit: one vote for the whole wave
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit) != 0 || defer_hit(d), 0)) return false;
+    if (DEFER && __builtin_expect(__builtin_amdgcn_ballot_w64(hit) != 0 || defer_hit(m), 0)) return false;
     out = r;
     return true;
 }
@@ -484,14 +397,15 @@ BP_DEV bool sm_lane_loop_d(ge& out, const fe& s, const geq* q, const ge* __restr
 template <bool QLDS, bool FORCE = false>
 BP_DEV ge sm_lane(const fe& s, const geq* q, const ge* __restrict__ dtab, const ge* ptab, int K) {
     const bool zone = __all(fe_is_one(qget<QLDS>(&q->Z)));
-#if BP_LANE_DEFER
     ge r;
-    if (zone ? sm_lane_loop_d<QLDS, true, FORCE>(r, s, q, dtab, ptab, K)
-             : sm_lane_loop_d<QLDS, false, FORCE>(r, s, q, dtab, ptab, K))
+#if BP_LANE_DEFER
+    if (zone ? sm_lane_loop<QLDS, true, true, FORCE>(r, s, q, dtab, ptab, K)
+             : sm_lane_loop<QLDS, false, true, FORCE>(r, s, q, dtab, ptab, K))
         return r;
 #endif
-    if (zone) return sm_lane_loop<QLDS, true>(s, q, dtab, ptab, K);
-    return sm_lane_loop<QLDS, false>(s, q, dtab, ptab, K);
+    if (zone) sm_lane_loop<QLDS, true, false>(r, s, q, dtab, ptab, K);
+    else sm_lane_loop<QLDS, false, false>(r, s, q, dtab, ptab, K);
+    return r;
 }
 
 // Wave-level dispatch: uniform scalar -> scalar-branch loop, else the per-lane loop.
@@ -499,7 +413,7 @@ BP_DEV ge sm_lane(const fe& s, const geq* q, const ge* __restrict__ dtab, const 
 // ptab / K: this lane's base's prefix table (nullable) and its width in bits (0: none).
 // The loops first run their deferred pass (above); when it reports a rare edge or a failed gate in
 // some lane the wave runs the same scalar multiplication again from its start state (s, the slot,
-// dtab, ptab and K are all still there) with the gated forms.  FORCE: see sm_uniform_d.
+// dtab, ptab and K are all still there) in the gated mode.  FORCE: see sm_uniform.
 template <bool QLDS, bool FORCE = false>
 BP_DEV ge scalarmult(const fe& s, const ge& P, geq* slot, const ge* __restrict__ dtab, const ge* ptab = nullptr,
                      int K = 0) {
@@ -526,11 +440,12 @@ BP_DEV ge scalarmult(const fe& s, const ge& P, geq* slot, const ge* __restrict__
         same &= (lo == __builtin_amdgcn_readfirstlane(lo)) & (hi == __builtin_amdgcn_readfirstlane(hi));
     }
     if (__all(same)) {
-#if BP_LANE_DEFER
         ge r;
-        if (sm_uniform_d<QLDS, FORCE>(r, s, q, dtab, ptab, K)) return r;
+#if BP_LANE_DEFER
+        if (sm_uniform<QLDS, true, FORCE>(r, s, q, dtab, ptab, K)) return r;
 #endif
-        return sm_uniform<QLDS>(s, q, dtab, ptab, K);
+        sm_uniform<QLDS, false>(r, s, q, dtab, ptab, K);
+        return r;
     }
     return sm_lane<QLDS, FORCE>(s, q, dtab, ptab, K);
 }

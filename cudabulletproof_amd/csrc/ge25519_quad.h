@@ -15,20 +15,23 @@
 #endif
 namespace bp {
 
-template <int SRC>
-__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, SRC * 0x55, 0xF, 0xF, true);
-}
-template <int SRC>
-__device__ __forceinline__ fe fe_quad_bcast(const fe& a) {
+// A field element's eight words moved through one DPP control; the named moves below are this one.
+template <int CTRL>
+__device__ __forceinline__ fe fe_dpp(const fe& a) {
     fe r;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        uint32_t lo = quad_bcast<SRC>((uint32_t)a.v[i]), hi = quad_bcast<SRC>((uint32_t)(a.v[i] >> 32));
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)a.v[i], CTRL, 0xF, 0xF, true);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(a.v[i] >> 32), CTRL, 0xF, 0xF, true);
         r.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
     }
     return r;
 }
+template <int SRC>   // lane SRC of each quad to the whole quad (quad_perm [SRC, SRC, SRC, SRC])
+__device__ __forceinline__ fe fe_quad_bcast(const fe& a) { return fe_dpp<SRC * 0x55>(a); }
+template <int SRC>   // lane SRC of each 16-lane row to the whole row (row_newbcast)
+__device__ __forceinline__ fe fe_row_bcast(const fe& a) { return fe_dpp<0x150 + SRC>(a); }
+__device__ __forceinline__ fe fe_pair_swap(const fe& a) { return fe_dpp<0xB1>(a); }   // lane l <- lane l ^ 1
 // (bit masks, not a ternary chain: the compiler turned that into a private array indexed by q,
 // i.e. scratch stores and loads inside the dependent chains)
 __device__ __forceinline__ fe fe_sel4(int q, const fe& a, const fe& b, const fe& c, const fe& d) {
@@ -107,18 +110,14 @@ __device__ __forceinline__ fe fe_q4_sum_fold(const uint32_t w[10], uint32_t* acc
 #endif
     uint64_t t[8];
 #pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = (uint64_t)r[2 * i] | ((uint64_t)r[2 * i + 1] << 32);
+    for (int i = 0; i < 8; i++) t[i] = cat64(r[2 * i], r[2 * i + 1]);
     return fe_fold512<LAT>(t, acc);
 }
 template <int LAT = 0>
 __device__ __forceinline__ fe fe_mul_q4(const fe& x, const fe& y, uint32_t* acc = nullptr) {
     uint32_t a[2], b[8], w[10];
     q4_rows(x, a);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        b[2 * i] = (uint32_t)y.v[i];
-        b[2 * i + 1] = (uint32_t)(y.v[i] >> 32);
-    }
+    fe_words(b, y);
     mul2x8_bounded_asm(w, a, b);   // the counting form when a lane's a[0] exceeds the bound (mul512_asm.h)
     if (__builtin_expect(__any(a[0] > MUL_BOUNDED_WORD), 0)) mul2x8_asm(w, a, b);
     return fe_q4_sum_fold<LAT>(w, acc);
@@ -163,17 +162,7 @@ __device__ __forceinline__ ge ge_op_quad(const ge& p, const ge& q) {
 // 0x104 (row_shl:4, lane l takes l+4).
 template <int CTRL>
 __device__ __forceinline__ ge ge_row_move(const ge& a) {
-    auto mv = [](const fe& f) {
-        fe r;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)f.v[i], CTRL, 0xF, 0xF, true);
-            uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(f.v[i] >> 32), CTRL, 0xF, 0xF, true);
-            r.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
-        }
-        return r;
-    };
-    return ge{mv(a.X), mv(a.Y), mv(a.Z), mv(a.T)};
+    return ge{fe_dpp<CTRL>(a.X), fe_dpp<CTRL>(a.Y), fe_dpp<CTRL>(a.Z), fe_dpp<CTRL>(a.T)};
 }
 
 // ge25519_scalarmult (curve25519_ops.cu:397-415) of one quad: s and P replicated over the quad's
@@ -194,17 +183,6 @@ __device__ __forceinline__ ge ge_row_move(const ge& a) {
 // quad_perm) to form Y3 - X3 and Y3 + X3 (fe_addsub: both chains in one block).  One step: 744 VALU
 // and 103 s_nop instead of 808 and 139 (tools/isa_count.py,
 // p_quad_step / p_quad_step_of); the products are the same (G F is the integer F G), so the bits.
-template <int CTRL>
-__device__ __forceinline__ fe fe_dpp(const fe& a) {
-    fe r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)a.v[i], CTRL, 0xF, 0xF, true);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(a.v[i] >> 32), CTRL, 0xF, 0xF, true);
-        r.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    return r;
-}
 // p: r in operand form, o = this lane's stage-1 operand; q = this lane's q-side operand (the
 // doubling passes o); returns the result's stage-3 product (X3 | T3 | Z3 | Y3 by lane)
 template <bool SQ = false>   // SQ: a doubling known to the whole wave (stage 1 as squares, q unused)
@@ -240,10 +218,8 @@ __device__ __forceinline__ ge quad_of_point(const fe& r3) {   // X3 | T3 | Z3 | 
 }
 __device__ __forceinline__ ge sm_quad(const fe& s, const ge& P, const ge* __restrict__ dtab, const ge* ptab, int K) {
     const fe qs = quad_of_form(P);
-    const int lz = fe_clz256(s);
-    const bool pre = K > 0 && lz < K && ptab != nullptr;
-    const ge r0 = *(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
-    int i = pre ? 255 - K : 255 - lz;   // index of the pending bit
+    int i;   // index of the pending bit
+    const ge r0 = sm_start(s, ptab, K, dtab, i);
     if (i < 0) return r0;
     BitStream bs = bs_init(s, i);
     uint32_t bit = bs_next(bs);
@@ -272,17 +248,6 @@ __device__ __forceinline__ ge sm_quad(const fe& s, const ge& P, const ge* __rest
 // the row over row_newbcast; quads 0 and 3 swap X3 / Y3 over row_mirror (quad q <-> quad 3 - q;
 // the values are replicated over each quad, so the mirrored lane order within a quad is moot).
 // The same 512-bit products and the same add / sub / fold code, so the same bits.
-template <int SRC>   // lane SRC of each 16-lane row to the whole row (DPP row_newbcast)
-__device__ __forceinline__ fe fe_row_bcast(const fe& a) {
-    fe r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)a.v[i], 0x150 + SRC, 0xF, 0xF, true);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(a.v[i] >> 32), 0x150 + SRC, 0xF, 0xF, true);
-        r.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    return r;
-}
 // BP_ROW_LAT: the row step's field blocks in their latency forms (field_asm.h *_lat: m = carry | top in
 // VALU, no SALU OR waiting on a compare; 2 more VALU per block, which the one wave per SIMD of a row tick
 // does not feel)
@@ -327,10 +292,8 @@ __device__ __forceinline__ ge row_of_point(const fe& r3) {   // X3 | T3 | Z3 | Y
 #endif
 __device__ __forceinline__ ge sm_row(const fe& s, const ge& P, const ge* __restrict__ dtab, const ge* ptab, int K) {
     const fe qs = row_of_form(P);
-    const int lz = fe_clz256(s);
-    const bool pre = K > 0 && lz < K && ptab != nullptr;
-    const ge r0 = *(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
-    int i = pre ? 255 - K : 255 - lz;   // index of the pending bit
+    int i;   // index of the pending bit
+    const ge r0 = sm_start(s, ptab, K, dtab, i);
     if (i < 0) return r0;
     BitStream bs = bs_init(s, i);
     uint32_t bit = bs_next(bs);
@@ -397,16 +360,6 @@ __device__ __forceinline__ ge sm_row(const fe& s, const ge& P, const ge* __restr
 // already the next operands and the pair swaps X3 / Y3 to form Y3 - X3 / Y3 + X3 (fe_addsub).  5
 // product latencies per point operation instead of 9, with 10 products per operation instead of 9
 // (a quad forms 12): the form for ticks that fill the SIMDs at two lanes per item but not at four.
-__device__ __forceinline__ fe fe_pair_swap(const fe& a) {   // lane l <- lane l ^ 1
-    fe r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)a.v[i], 0xB1, 0xF, 0xF, true);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(a.v[i] >> 32), 0xB1, 0xF, 0xF, true);
-        r.v[i] = (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    return r;
-}
 __device__ __forceinline__ void pair_of_form(const ge& r, fe& oa, fe& ob) {
     const bool odd = threadIdx.x & 1;
     fe s, d;
@@ -435,10 +388,8 @@ __device__ __forceinline__ ge sm_pair(const fe& s, const ge& P, const ge* __rest
     const bool odd = threadIdx.x & 1;
     fe qa, qb;   // this lane's q-side operands
     pair_of_form(P, qa, qb);
-    const int lz = fe_clz256(s);
-    const bool pre = K > 0 && lz < K && ptab != nullptr;
-    const ge r0 = *(pre ? &ptab[prefix_index(s, K)] : &dtab[lz]);
-    int i = pre ? 255 - K : 255 - lz;   // index of the pending bit
+    int i;   // index of the pending bit
+    const ge r0 = sm_start(s, ptab, K, dtab, i);
     if (i < 0) return r0;
     BitStream bs = bs_init(s, i);
     uint32_t bit = bs_next(bs);

@@ -1,5 +1,5 @@
-"""The lane loops' deferred rare-edge and gate tests (ge25519_dev.h: ge_dbl_d, ge_add_qp_d,
-ge_add_sel_d; fe25519_dev.h LAT 3), checked on the CPU from the emitted text.
+"""The lane loops' deferred rare-edge and gate tests (ge25519_dev.h: the point forms in the Defer
+mode; fe25519_dev.h LAT 3), checked on the CPU from the emitted text.
 
 * field_asm.h's throughput *_acc statements are their split block's fast statement with the one
   rare-edge compare replaced by the running max into acc: the same instructions otherwise.
@@ -134,19 +134,53 @@ def test_gate_word_exceeds_bound_exactly_when_the_gate_fails():
         assert nxt[1].strip().startswith(f"else if (__builtin_expect(__any(max({words_}) > MUL_BOUNDED_WORD), 0))")
 
 
+def _body(src, head):
+    body = src[src.index(head):]
+    return body[:body.index("\n}\n")]
+
+
 def test_loops_run_the_deferred_forms_and_rerun_on_a_hit():
-    """ge25519_dev.h: the deferred point forms use only LAT 3 field calls (fe_mul_one keeps its own
-    test), the two loops test the running words once per chunk and once after the loop, and
-    scalarmult / sm_lane fall through to the gated loops when the deferred pass reports a hit."""
+    """ge25519_dev.h: the point forms reach their field blocks only through the mode's forwards, whose
+    Defer mode is LAT 3 with both running words and whose Gated mode is LAT 0 (fe_mul_one keeps its own
+    test), the two loops' deferred instantiation tests the running words once per chunk and once after
+    the loop and warms up with the gated overload, and scalarmult / sm_lane fall through to the gated
+    instantiation when the deferred pass reports a hit."""
     src = open(os.path.join(CSRC, "ge25519_dev.h")).read()
-    for fn in ("ge_dbl_d", "ge_add_qp_d", "ge_add_sel_d"):
-        body = src[src.index(f"BP_DEV ge {fn}("):]
-        body = body[:body.index("\n}\n")]
-        calls = re.findall(r"\b(fe_(?:add|sub|mul|sq|mul_k|addsub)|lane_addsub\w*)(<\d>)?\(", body)
-        assert calls and all(t == "<3>" or name == "lane_addsub_d" for name, t in calls), (fn, calls)
-    for fn in ("sm_uniform_d", "sm_lane_loop_d"):
-        body = src[src.index(f"BP_DEV bool {fn}("):]
-        body = body[:body.index("\n}\n")]
-        assert body.count("defer_hit(d)") == 2 and "BP_DEFER_CHUNK" in body
+    # (a) no point form calls a field block with a literal mode
+    field = r"\bfe_(?:add|sub|mul|sq|mul_k|addsub)\b"
+    for head in ("BP_DEV ge ge_tail(", "BP_DEV ge ge_dbl(const ge& p, M& m)", "BP_DEV ge ge_add_qp(const ge& p, const geq* q, bool zone, M& m)",
+                 "BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q, M& m)"):
+        body = _body(src, head)
+        assert re.findall(r"\bm_(?:add|sub|mul|sq|mul_k|addsub)\(", body) and not re.findall(field, body), head
+    assert len(re.findall(r"\bBP_DEV ge (?:ge_tail|ge_dbl|ge_add_qp|ge_add_sel)\(", src)) == 7   # + the three gated overloads
+    assert not re.search(r"\b\w+_d\b\s*[<(]", src)                                             # no second family
+    forwards = {m.group(1): m.group(2) for m in re.finditer(r"BP_DEV \w+ m_(\w+)\(.*?\) \{(.*?)\n?\}\n", src, re.S)}
+    assert sorted(forwards) == ["add", "addsub", "mul", "mul_k", "sq", "sub"]
+    for name, body in forwards.items():
+        calls = re.findall(r"\b(fe_\w+)<([^>]*)>\(([^;]*)\);", body)
+        assert calls and all(t == "M::LAT" and "m.edge()" in args for _, t, args in calls), (name, calls)
+        assert all(("m.gate()" in args) == (fn in ("fe_mul", "fe_sq")) for fn, _, args in calls), (name, calls)
+    assert {fn for fn, _, _ in re.findall(r"\b(fe_\w+)<([^>]*)>\(([^;]*)\);", forwards["addsub"])} == {"fe_addsub", "fe_sub", "fe_add"}
+    gated, defer = _body(src, "struct Gated {"), _body(src, "struct Defer {")
+    assert "LAT = 0;" in gated and gated.count("return nullptr;") == 2
+    assert "LAT = 3;" in defer and "edge() { return &acc; }" in defer and "gate() { return &gacc; }" in defer
+    # (b), (c) each loop: two tests of the running words in the deferred instantiation only, the warm-up gated
+    for head, warm in (("BP_DEV bool sm_uniform(", "r = ge_dbl(r);"), ("BP_DEV bool sm_lane_loop(", "r = ge_add_sel<QLDS, ZONE>(r, q, add_phase);")):
+        body = _body(src, head)
+        tests = [l.strip() for l in body.splitlines() if "defer_hit(m)" in l]
+        assert len(tests) == 2 and body.count("defer_hit(") == 2 and "BP_DEFER_CHUNK" in body
+        assert "std::conditional_t<DEFER, Defer, Gated> m;" in body
+        chunk = body[body.index("if (DEFER && ++n == BP_DEFER_CHUNK) {"):]
+        assert tests[0] in chunk[:chunk.index("\n        }\n")] and tests[1].startswith("if (DEFER && ")
+        w = body.index(warm)
+        assert "DEFER" in body[:w].splitlines()[-1] + body[:w].splitlines()[-2] and w < body.index("conditional_t")
+    assert "ge_add_qp<QLDS>(r, q, zone);" in _body(src, "BP_DEV bool sm_uniform(").split("conditional_t")[0]
+    # (d) the gated instantiation after a deferred pass that returned false
     sm = src[src.index("BP_DEV ge scalarmult("):]
-    assert re.search(r"if \(sm_uniform_d<QLDS, FORCE>\(r, s, q, dtab, ptab, K\)\) return r;\s*#endif\s*return sm_uniform<QLDS>\(", sm)
+    assert re.search(r"#if BP_LANE_DEFER\s*if \(sm_uniform<QLDS, true, FORCE>\(r, s, q, dtab, ptab, K\)\) return r;\s*#endif\s*"
+                     r"sm_uniform<QLDS, false>\(r, s, q, dtab, ptab, K\);\s*return r;", sm)
+    lane = _body(src, "BP_DEV ge sm_lane(")
+    assert re.search(r"#if BP_LANE_DEFER\s*if \(zone \? sm_lane_loop<QLDS, true, true, FORCE>\(r, s, q, dtab, ptab, K\)\s*"
+                     r": sm_lane_loop<QLDS, false, true, FORCE>\(r, s, q, dtab, ptab, K\)\)\s*return r;\s*#endif\s*"
+                     r"if \(zone\) sm_lane_loop<QLDS, true, false>\(r, s, q, dtab, ptab, K\);\s*"
+                     r"else sm_lane_loop<QLDS, false, false>\(r, s, q, dtab, ptab, K\);\s*return r;", lane)

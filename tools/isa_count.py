@@ -38,16 +38,21 @@ def main():
     for name in [l.split(":")[0] for l in s.split("\n") if l.startswith("p_") and l.split(":")[0].isidentifier()]:
         body = s[s.index("\n" + name + ":"):]
         body = body[:body.index("s_endpgm")]
-        if name.startswith("p_sm_"):   # a loop kernel: the last backward branch's body (one iteration)
+        if name.startswith("p_sm_"):
+            # a loop kernel: the innermost backward branch's body that holds the point step, i.e. the one with
+            # the most products (the last of equals: a deferred pass comes after its gated warm-up step)
             lines = body.split("\n")
             labels = {l.split(":")[0]: i for i, l in enumerate(lines) if re.match(r"^\.LBB\d+_\d+:", l)}
-            span = None
+            spans = []
             for i, l in enumerate(lines):
                 m = re.search(r"s_(?:cbranch_\w+|branch)\s+(\.LBB\d+_\d+)", l)
                 if m and m.group(1) in labels and labels[m.group(1)] < i:
-                    span = (labels[m.group(1)], i)
-            if span:
-                body = "\n".join(lines[span[0]:span[1] + 1])
+                    spans.append((labels[m.group(1)], i))
+            inner = [(a, b) for a, b in spans if not any((c, d) != (a, b) and a <= c and d <= b for c, d in spans)]
+            if inner:
+                mads = lambda ab: sum("v_mad_u64_u32" in l for l in lines[ab[0]:ab[1] + 1])
+                a, b = max(reversed(inner), key=mads)
+                body = "\n".join(lines[a:b + 1])
                 name += " (loop body)"
         # the field asm's exact forms for rare edges sit between "s_branch 4f" and the "4:" label:
         # count the common path only (what a wave executes unless a lane is on a rare edge)

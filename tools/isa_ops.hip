@@ -28,24 +28,24 @@ extern "C" __global__ void p_ge_add_sel_zone(ge* o, const ge* p, const geq* q, c
     qs[threadIdx.x] = q[threadIdx.x];
     o[threadIdx.x] = ge_add_sel<true, true>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0);
 }
-// the deferred forms (ge25519_dev.h: the lane loops' common pass), the running test words written out
+// the same forms in the Defer mode (ge25519_dev.h: the lane loops' common pass), the running test words written out
 extern "C" __global__ void p_ge_dbl_d(ge* o, const ge* p, uint32_t* w) {
     Defer d;
-    o[threadIdx.x] = ge_dbl_d(p[threadIdx.x], d);
+    o[threadIdx.x] = ge_dbl(p[threadIdx.x], d);
     w[threadIdx.x] = d.acc | d.gacc;
 }
 extern "C" __global__ void p_ge_add_zone_d(ge* o, const ge* p, const geq* q, uint32_t* w) {
     __shared__ geq qs[256];
     qs[threadIdx.x] = q[threadIdx.x];
     Defer d;
-    o[threadIdx.x] = ge_add_qp_d<true>(p[threadIdx.x], &qs[threadIdx.x], true, d);
+    o[threadIdx.x] = ge_add_qp<true>(p[threadIdx.x], &qs[threadIdx.x], true, d);
     w[threadIdx.x] = d.acc | d.gacc;
 }
 extern "C" __global__ void p_ge_add_sel_zone_d(ge* o, const ge* p, const geq* q, const int* u, uint32_t* w) {
     __shared__ geq qs[256];
     qs[threadIdx.x] = q[threadIdx.x];
     Defer d;
-    o[threadIdx.x] = ge_add_sel_d<true, true>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0, d);
+    o[threadIdx.x] = ge_add_sel<true, true>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0, d);
     w[threadIdx.x] = d.acc | d.gacc;
 }
 extern "C" __global__ void p_fe_canon(fe* o, const fe* a) { o[threadIdx.x] = fe_canon(a[threadIdx.x]); }
@@ -86,13 +86,15 @@ extern "C" __global__ void p_row_step_of(fe* o, const fe* p, const fe* qs, const
 extern "C" __global__ void p_sm_lane_zone(ge* o, const fe* s, const ge* p, const ge* dtab) {
     __shared__ geq qs[256];
     qs[threadIdx.x] = ge_prep(p[threadIdx.x]);
-    o[threadIdx.x] = sm_lane_loop<true, true>(s[threadIdx.x], &qs[threadIdx.x], dtab, nullptr, 0);
+    ge r;
+    sm_lane_loop<true, true, false>(r, s[threadIdx.x], &qs[threadIdx.x], dtab, nullptr, 0);
+    o[threadIdx.x] = r;
 }
-// the same loop's deferred pass (sm_lane_loop_d), a hit reported through the flag word
+// the same loop's deferred pass (DEFER = true), a hit reported through the flag word
 extern "C" __global__ void p_sm_lane_zone_d(ge* o, const fe* s, const ge* p, const ge* dtab, uint32_t* w) {
     __shared__ geq qs[256];
     qs[threadIdx.x] = ge_prep(p[threadIdx.x]);
     ge r = ge_zero();
-    w[threadIdx.x] = sm_lane_loop_d<true, true, false>(r, s[threadIdx.x], &qs[threadIdx.x], dtab, nullptr, 0);
+    w[threadIdx.x] = sm_lane_loop<true, true, true>(r, s[threadIdx.x], &qs[threadIdx.x], dtab, nullptr, 0);
     o[threadIdx.x] = r;
 }
