@@ -130,6 +130,7 @@ EXPORTS = [
     "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host",
     "hipbp_batch_generate_range_proof_accepted", "hipbp_batch_generate_range_proof_accepted_gens",
     "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats",
+    "hipbp_batch_generate_range_proof_host_sharded", "hipbp_batch_generate_range_proof_accepted_host",
 ]
 
 
@@ -161,7 +162,8 @@ def lib():
                   "hipbp_derive_prover_scalars", "hipbp_batch_generate_range_proof_seeded",
                   "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host",
                   "hipbp_batch_generate_range_proof_accepted", "hipbp_batch_generate_range_proof_accepted_gens",
-                  "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats"):
+                  "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats",
+                  "hipbp_batch_generate_range_proof_host_sharded", "hipbp_batch_generate_range_proof_accepted_host"):
             getattr(L, f).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -646,26 +648,18 @@ def _take(vec, words):
 _take.free = None   # libc's free, looked up on first use
 
 
-def batch_generate_range_proof_host(v, gamma, n, G, H, g, h, seed, index_base=0):
-    """hipbp_batch_generate_range_proof_host: the seeded prover on host arrays, through the
-    reference's own RangeProof structs.  v, gamma (count,4), G, H (n,16), g, h (16,) uint64; seed 32
-    secret bytes.  Returns (proofs, valid): a list of the proof dicts cuda_range_proof_verify and
-    batch_range_proof_verify_host take (head (100,) = V,A,S,T1,T2 | taux,mu,t,c,x; a, b (1,4); L, R
-    (log2 n,16)) and a (count,) bool array.  A refused value (valid False) has the zeroed proof:
-    empty a, b, L, R.  Synchronous, on the current device."""
-    require_gpu()
+def _host_prove_args(v, gamma, G, H, g, h, seed):
+    """The host provers' arguments as the C ABI takes them: (seed buffer, v, gamma, G, H, g, h, count)."""
     sd = _seed_arg(seed)
     v, gamma = _u64(v, 4).reshape(-1, 4), _u64(gamma, 4).reshape(-1, 4)
     if len(v) != len(gamma):
         raise ValueError("v and gamma must have the same length")
     G, H, g, h = _u64(G, 16), _u64(H, 16), _u64(g, 16), _u64(h, 16)
-    count = len(v)
-    arr = (RangeProofC * max(count, 1))()
-    valid = np.zeros(max(count, 1), np.uint8)
-    gv, hv = PointVector(_p(G).value, len(G)), PointVector(_p(H).value, len(H))
-    _chk(lib().hipbp_batch_generate_range_proof_host(arr, _p(valid), _p(v), _p(gamma), _sz(count), _sz(int(n)),
-                                                     ctypes.byref(gv), ctypes.byref(hv), _p(g), _p(h), sd,
-                                                     ctypes.c_uint64(int(index_base) & (2**64 - 1))))
+    return sd, v, gamma, G, H, g, h, len(v)
+
+
+def _take_proofs(arr, count):
+    """The structs a host prover filled as proof dicts; every vector is freed through _take."""
     proofs = []
     for i in range(count):
         rp = arr[i]
@@ -674,7 +668,48 @@ def batch_generate_range_proof_host(v, gamma, n, G, H, g, h, seed, index_base=0)
                               [np.array(ip.c, np.uint64), np.array(ip.x, np.uint64)])
         proofs.append(dict(head=head, a=_take(ip.a, 4), b=_take(ip.b, 4), L=_take(ip.L, 16), R=_take(ip.R, 16),
                            n=int(ip.n), L_len=int(ip.L_len)))
-    return proofs, valid[:count].astype(bool)
+    return proofs
+
+
+def batch_generate_range_proof_host(v, gamma, n, G, H, g, h, seed, index_base=0, num_gpus=1):
+    """hipbp_batch_generate_range_proof_host_sharded: the seeded prover on host arrays, through the
+    reference's own RangeProof structs.  v, gamma (count,4), G, H (n,16), g, h (16,) uint64; seed 32
+    secret bytes.  Returns (proofs, valid): a list of the proof dicts cuda_range_proof_verify and
+    batch_range_proof_verify_host take (head (100,) = V,A,S,T1,T2 | taux,mu,t,c,x; a, b (1,4); L, R
+    (log2 n,16)) and a (count,) bool array.  A refused value (valid False) has the zeroed proof:
+    empty a, b, L, R.  Synchronous.  num_gpus: the devices the batch is split over, from the current
+    one on (1: the current device alone; 0: all visible); the result does not depend on it."""
+    require_gpu()
+    sd, v, gamma, G, H, g, h, count = _host_prove_args(v, gamma, G, H, g, h, seed)
+    arr = (RangeProofC * max(count, 1))()
+    valid = np.zeros(max(count, 1), np.uint8)
+    gv, hv = PointVector(_p(G).value, len(G)), PointVector(_p(H).value, len(H))
+    _chk(lib().hipbp_batch_generate_range_proof_host_sharded(arr, _p(valid), _p(v), _p(gamma), _sz(count), _sz(int(n)),
+                                                             ctypes.byref(gv), ctypes.byref(hv), _p(g), _p(h), sd,
+                                                             ctypes.c_uint64(int(index_base) & (2**64 - 1)),
+                                                             ctypes.c_int(num_gpus)))
+    return _take_proofs(arr, count), valid[:count].astype(bool)
+
+
+def batch_generate_range_proof_accepted_host(v, gamma, n, G, H, g, h, seed, index_base=0, max_attempts=8, check=1,
+                                             num_gpus=1):
+    """hipbp_batch_generate_range_proof_accepted_host: the accepted prover on host
+    arrays; batch_generate_range_proof_host's arguments and proof dicts, batch_generate_range_proof_accepted's
+    max_attempts and check.  Returns (proofs, valid, attempts): attempts (count,) uint8, k >= 1 accepted
+    at the k-th attempt; 0 refused (valid False, the zeroed proof) or not accepted within max_attempts
+    (valid True, the last attempt's proof).  accepted_last_stats() afterwards reports the whole call."""
+    require_gpu()
+    sd, v, gamma, G, H, g, h, count = _host_prove_args(v, gamma, G, H, g, h, seed)
+    arr = (RangeProofC * max(count, 1))()
+    valid = np.zeros(max(count, 1), np.uint8)
+    attempts = np.zeros(max(count, 1), np.uint8)
+    gv, hv = PointVector(_p(G).value, len(G)), PointVector(_p(H).value, len(H))
+    _chk(lib().hipbp_batch_generate_range_proof_accepted_host(arr, _p(valid), _p(attempts), _p(v), _p(gamma), _sz(count),
+                                                              _sz(int(n)), ctypes.byref(gv), ctypes.byref(hv), _p(g),
+                                                              _p(h), sd, ctypes.c_uint64(int(index_base) & (2**64 - 1)),
+                                                              ctypes.c_int(max_attempts), ctypes.c_int(check),
+                                                              ctypes.c_int(num_gpus)))
+    return _take_proofs(arr, count), valid[:count].astype(bool), attempts[:count].copy()
 
 
 def batch_inner_product_prove(n, a, b, c, G, H, Q, transcript=None, stream=None, gens=None):

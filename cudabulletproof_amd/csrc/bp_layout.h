@@ -72,12 +72,14 @@ struct ChunkLayout {
 // ------------------------------------------------------------------ proof vectors
 // A proof's a, b (length 1) and L, R (Lr points; 1 byte when Lr = 0) malloc'ed as the reference's
 // inner_product_proof_init / field_vector_copy leave them, and n and the lengths set.  False: an
-// allocation failed (what was allocated is in the proof, for the caller to free).
-inline bool proof_vectors_alloc(InnerProductProof& ip, size_t n, size_t Lr) {
-    ip.a.elements = (fe25519*)malloc(FE);
-    ip.b.elements = (fe25519*)malloc(FE);
-    ip.L.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
-    ip.R.elements = (ge25519*)malloc(Lr ? Lr * GE : 1);
+// allocation failed (what was allocated is in the proof, for the caller to free).  `alloc`: malloc,
+// or what stands in for it in a CPU check.
+typedef void* (*AllocFn)(size_t);
+inline bool proof_vectors_alloc(InnerProductProof& ip, size_t n, size_t Lr, AllocFn alloc = malloc) {
+    ip.a.elements = (fe25519*)alloc(FE);
+    ip.b.elements = (fe25519*)alloc(FE);
+    ip.L.elements = (ge25519*)alloc(Lr ? Lr * GE : 1);
+    ip.R.elements = (ge25519*)alloc(Lr ? Lr * GE : 1);
     ip.n = n;
     ip.a.length = ip.b.length = 1;
     ip.L.length = ip.R.length = ip.L_len = Lr;
@@ -113,7 +115,7 @@ struct OutLayout {
     // Proof k of a host copy into p (n = 1 << Lr): 1 a valid proof, its vectors malloc'ed; 0 a refused
     // one (the five points and taux, mu, t; ip_proof all zero); -1 an allocation failed (p owns what
     // was allocated)
-    int unpack(const void* base, size_t k, size_t n, RangeProof& p) const {
+    int unpack(const void* base, size_t k, size_t n, RangeProof& p, AllocFn alloc = malloc) const {
         hipbp_proof_out o;
         view(const_cast<void*>(base), &o);   // (read only)
         p.V = o.V[k]; p.A = o.A[k]; p.S = o.S[k]; p.T1 = o.T1[k]; p.T2 = o.T2[k];
@@ -121,7 +123,7 @@ struct OutLayout {
         InnerProductProof& ip = p.ip_proof;
         memset(&ip, 0, sizeof ip);
         if (!o.valid[k]) return 0;
-        if (!proof_vectors_alloc(ip, n, Lr)) return -1;
+        if (!proof_vectors_alloc(ip, n, Lr, alloc)) return -1;
         ip.c = o.c[k]; ip.x = o.x[k];
         *ip.a.elements = o.a[k]; *ip.b.elements = o.b[k];
         if (Lr) {

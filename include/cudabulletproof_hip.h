@@ -349,12 +349,48 @@ int hipbp_accepted_last_stats(int* rounds, uint32_t* proved, float* kernel_ms);
  * (V, A, S, T1, T2 identity; taux, mu, t 0) with ip_proof all zero (NULL vectors: freeing is safe).
  * Large counts go through in chunks (HIPBP_PROVE_HOST_CHUNK proofs, default 16384) that alternate
  * over the engine's two streams, each chunk with its own index_base.  On an error nothing stays
- * allocated and every proofs[i] is zero.  One device: a split over several devices would give
- * the same bits by the index design and is left for later. */
+ * allocated and every proofs[i] is zero.  It is hipbp_batch_generate_range_proof_host_sharded at
+ * num_gpus = 1. */
 int hipbp_batch_generate_range_proof_host(RangeProof* proofs, uint8_t* valid, const fe25519* v, const fe25519* gamma,
                                           size_t count, size_t n, const PointVector* G, const PointVector* H,
                                           const ge25519* g, const ge25519* h, const uint8_t seed32[32],
                                           uint64_t index_base);
+/* The same, split over several devices; the bytes do not depend on the split.  num_gpus as in
+ * hipbp_batch_range_proof_verify_host: <= 0 all visible devices; more than are visible HIPBP_ERR_ARG
+ * ("num_gpus = K but N HIP device(s) visible"), nothing written.  Shard d proves the contiguous block
+ * [count d / ng, count (d + 1) / ng) with index_base + its first index (mod 2^64) on device
+ * (current + d) mod the device count, in a host thread of its own (an empty block starts none; a
+ * call of one shard runs it on the caller's thread), so num_gpus = 1 stays on the caller's device;
+ * the caller's current device is restored on return.
+ * Inside a shard the chunks are as above.  HIPBP_HOST_SHARDS=k, read only when num_gpus <= 0: k
+ * shards (at most 64, at most one per proof), shard d on device (current + d) % the device count;
+ * shards that share a device run one after another.  Argument errors (a null pointer, a bad n,
+ * G->length != n, too many GPUs) write nothing; count = 0 returns HIPBP_OK.  A failure in any shard
+ * (a HIP error, a failed malloc) is reported as "device d: ..." after every thread was joined: every
+ * vector handed out in every shard is freed and proofs and valid are zero throughout. */
+int hipbp_batch_generate_range_proof_host_sharded(RangeProof* proofs, uint8_t* valid, const fe25519* v,
+                                                  const fe25519* gamma, size_t count, size_t n, const PointVector* G,
+                                                  const PointVector* H, const ge25519* g, const ge25519* h,
+                                                  const uint8_t seed32[32], uint64_t index_base, int num_gpus);
+/* The accepted prover on host data: proofs[i], valid[i] and attempts[i] (HOST, [count]) are what
+ * hipbp_batch_generate_range_proof_accepted gives for the same inputs, index_base, max_attempts
+ * (1..16) and check (1 or 2).  attempts[i] = k >= 1: accepted at the k-th attempt, the struct holds
+ * that proof.  attempts[i] = 0 with valid[i] = 0: a refused value, the zeroed proof with an all-zero
+ * ip_proof; with valid[i] = 1: not accepted within max_attempts, the struct holds the last
+ * attempt's proof.  Filled structs are as hipbp_batch_generate_range_proof_host leaves them.
+ * Synchronous; num_gpus, the split, HIPBP_HOST_SHARDS, the argument errors (also max_attempts,
+ * check, a null attempts) and the failure behaviour (attempts zeroed too) as in _host_sharded.
+ * A shard runs ONE accepted device call per chunk of HIPBP_PROVE_HOST_ACCEPT_CHUNK proofs (default
+ * 65536, at most 2^22: the retry rounds' fixed cost is per call) and brings a chunk's output to the
+ * host in pieces of HIPBP_PROVE_HOST_CHUNK proofs through the seeded call's two pinned slots, a
+ * piece unpacked while the next one copies.  No prefix tables.  Afterwards
+ * hipbp_accepted_last_stats on the calling thread reports the call as a whole: rounds the largest
+ * round count of any chunk, proved[r] summed over all shards and chunks. */
+int hipbp_batch_generate_range_proof_accepted_host(RangeProof* proofs, uint8_t* valid, uint8_t* attempts,
+                                                   const fe25519* v, const fe25519* gamma, size_t count, size_t n,
+                                                   const PointVector* G, const PointVector* H, const ge25519* g,
+                                                   const ge25519* h, const uint8_t seed32[32], uint64_t index_base,
+                                                   int max_attempts, int check, int num_gpus);
 
 /* ---- prover: the stand-alone inner_product_prove (bulletproof_vectors.h:94,
  * bulletproof_vectors.cu:277-523) for any power-of-two length, batched, bit-exact: the reference's

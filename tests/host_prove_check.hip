@@ -1,0 +1,197 @@
+// host_prove_check.hip — TEST INFRASTRUCTURE (tests/test_host_prove_plan.py).
+//
+// Runs the host provers' plan and result owner (cudabulletproof_amd/csrc/bp_host_prove.h, host-only)
+// on the CPU.
+//   plan:   over count x ng x chunk x index_base the shards are contiguous, disjoint, cover [0, count),
+//           differ in size by at most one, none empty when ng <= count; every shard's chunks cover it
+//           in order and carry index_base + c0 mod 2^64 (restated here with 128-bit arithmetic); the
+//           wrap past 2^64 is reached
+//   owner:  9 proofs (L_len 0 and 4, one refused value, with and without attempts) filled from three
+//           threads through a counting allocator, then rolled back: no vector left, every output byte
+//           zero; the same with the k-th allocation failing, for every k up to the total
+// Prints "<checks> <failures>"; exit status 1 on any failure.
+#include <atomic>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <set>
+#include <thread>
+#include <vector>
+
+#include "../cudabulletproof_amd/csrc/bp_host_prove.h"
+
+typedef unsigned long long u64;
+static std::atomic<u64> checks(0), fails(0);
+#define CHECK(cond, ...)                                    \
+    do {                                                    \
+        checks++;                                           \
+        if (!(cond)) {                                      \
+            if (fails++ < 20) {                             \
+                std::printf("FAIL line %d: ", __LINE__);    \
+                std::printf(__VA_ARGS__);                   \
+                std::printf("\n");                          \
+            }                                               \
+        }                                                   \
+    } while (0)
+
+static bool all_zero(const void* p, size_t len) {
+    for (size_t i = 0; i < len; i++) if (((const uint8_t*)p)[i]) return false;
+    return true;
+}
+
+// ------------------------------------------------------------------ plan
+static void plan() {
+    const size_t counts[] = {1, 2, 3, 9, 70, 65537}, chunks[] = {1, 4, 16384};
+    const int ngs[] = {1, 2, 3, 8, 64};
+    const uint64_t bases[] = {0, (uint64_t(1) << 32) - 3, ~uint64_t(0) - 1};   // 0, 2^32 - 3, 2^64 - 2
+    u64 wraps = 0, multi_chunk = 0, short_last = 0;
+    for (size_t count : counts)
+        for (int ng : ngs)
+            for (size_t chunk : chunks)
+                for (uint64_t base : bases) {
+                    const std::vector<bp::HostShard> sh = bp::plan_host_shards(count, ng);
+                    CHECK(!sh.empty() && sh.front().lo == 0 && sh.back().hi == count, "cover count=%zu ng=%d", count, ng);
+                    CHECK(sh.size() == std::min<size_t>(count, (size_t)ng), "shards %zu count=%zu ng=%d", sh.size(), count, ng);
+                    size_t smin = count, smax = 0;
+                    for (size_t k = 0; k < sh.size(); k++) {
+                        const size_t sz = sh[k].hi - sh[k].lo;
+                        CHECK(sh[k].hi > sh[k].lo, "empty shard listed");
+                        CHECK(sh[k].d >= 0 && sh[k].d < ng && (k == 0 || sh[k].d > sh[k - 1].d), "shard ids");
+                        CHECK(k == 0 || sh[k].lo == sh[k - 1].hi, "shards not contiguous");
+                        CHECK(sh[k].lo == count * (size_t)sh[k].d / ng && sh[k].hi == count * (size_t)(sh[k].d + 1) / ng,
+                              "block bounds");
+                        smin = std::min(smin, sz);
+                        smax = std::max(smax, sz);
+                        // the shard's chunks, cut as the library cuts them
+                        const size_t ch = std::min(chunk, sz);
+                        const std::vector<bp::HostChunk> cs = bp::plan_host_chunks(sh[k], ch, base);
+                        CHECK(cs.size() == (sz + ch - 1) / ch, "chunk count");
+                        size_t at = sh[k].lo;
+                        for (size_t q = 0; q < cs.size(); q++) {
+                            CHECK(cs[q].c0 == at, "chunk %zu starts at %zu, want %zu", q, cs[q].c0, at);
+                            CHECK(cs[q].c >= 1 && cs[q].c <= ch && (cs[q].c == ch || q + 1 == cs.size()), "chunk size");
+                            const uint64_t want = (uint64_t)((unsigned __int128)base + (unsigned __int128)cs[q].c0);
+                            CHECK(cs[q].index_base == want, "chunk base");
+                            if (cs[q].index_base < base) wraps++;
+                            if (cs[q].c < ch) short_last++;
+                            at += cs[q].c;
+                        }
+                        CHECK(at == sh[k].hi, "chunks end at %zu, want %zu", at, sh[k].hi);
+                        if (cs.size() > 1) multi_chunk++;
+                    }
+                    CHECK(smax - smin <= 1, "sizes differ by %zu", smax - smin);
+                    if ((size_t)ng <= count) CHECK(sh.size() == (size_t)ng && smin >= 1, "an empty shard at ng <= count");
+                }
+    CHECK(wraps > 0, "the wrap past 2^64 was never reached");
+    CHECK(multi_chunk > 0 && short_last > 0, "the grid has no shard of several chunks / no short last chunk");
+}
+
+// ------------------------------------------------------------------ owner
+// the allocator handed to the owner: counts, fails the fail_at-th call, tracks what is live
+static std::mutex g_mu;
+static std::set<void*> g_live;
+static std::atomic<long> g_calls(0);
+static long g_fail_at = 0;   // 0: never
+static void* t_alloc(size_t bytes) {
+    const long k = ++g_calls;
+    if (k == g_fail_at) return nullptr;
+    void* p = malloc(bytes);
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_live.insert(p);
+    return p;
+}
+static void t_release(void* p) {
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        CHECK(g_live.erase(p) == 1, "released a pointer the allocator did not hand out (or twice)");
+    }
+    free(p);
+}
+
+static void pattern(void* p, size_t len, u64 seed) {
+    uint8_t* q = (uint8_t*)p;
+    for (size_t i = 0; i < len; i++) {
+        seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+        q[i] = (uint8_t)(seed >> 56) | 1;   // never zero
+    }
+}
+
+// B proofs of Lr rounds, proof `refused` refused, as the host copy of a chunk's output; filled by
+// three threads (blocks of the plan), with the fail_at-th allocation failing (0: none)
+static void owner_case(size_t Lr, bool with_attempts, long fail_at) {
+    const size_t B = 9, refused = 5, n = size_t(1) << Lr;
+    const bp::OutLayout lay{B, B, Lr, 64};
+    std::vector<uint8_t> host(lay.slot_bytes());
+    pattern(host.data(), host.size(), 77 + Lr);
+    hipbp_proof_out o;
+    lay.view(host.data(), &o);
+    for (size_t k = 0; k < B; k++) o.valid[k] = k != refused;
+    std::vector<RangeProof> proofs(B);
+    std::vector<uint8_t> valid(B), attempts(B);
+    pattern(proofs.data(), B * sizeof(RangeProof), 5);   // the owner zeroes what it is given
+    pattern(valid.data(), B, 6);
+    pattern(attempts.data(), B, 7);
+    g_calls = 0;
+    g_fail_at = fail_at;
+    bp::ProofOwner own(proofs.data(), valid.data(), with_attempts ? attempts.data() : nullptr, B,
+                       bp::HostAlloc{t_alloc, t_release});
+    CHECK(all_zero(proofs.data(), B * sizeof(RangeProof)) && all_zero(valid.data(), B), "outputs not zeroed at the start");
+    CHECK(!with_attempts || all_zero(attempts.data(), B), "attempts not zeroed at the start");
+    std::atomic<int> failed(0);
+    std::vector<std::thread> th;
+    for (const bp::HostShard& sh : bp::plan_host_shards(B, 3))
+        th.emplace_back([&, sh]() {
+            for (size_t i = sh.lo; i < sh.hi; i++)
+                if (!own.fill(i, lay, host.data(), i, n, (uint8_t)(i == refused ? 0 : i % 3 + 1))) {   // a shard stops at its first failure
+                    failed++;
+                    return;
+                }
+        });
+    for (auto& t : th) t.join();
+    const long total = 4 * (long)(B - 1);
+    if (fail_at == 0 || fail_at > total) {
+        CHECK(failed == 0 && g_calls == total, "allocations %ld, want %ld", (long)g_calls, total);
+        CHECK(g_live.size() == (size_t)total, "live vectors %zu", g_live.size());
+        for (size_t i = 0; i < B; i++) {
+            const RangeProof& p = proofs[i];
+            const InnerProductProof& ip = p.ip_proof;
+            CHECK(!memcmp(&p.V, &o.V[i], 128) && !memcmp(&p.T2, &o.T2[i], 128) && !memcmp(&p.mu, &o.mu[i], 32), "head %zu", i);
+            CHECK(valid[i] == (i != refused), "valid %zu", i);
+            if (with_attempts) CHECK(attempts[i] == (i == refused ? 0 : i % 3 + 1), "attempts %zu", i);
+            if (i == refused) {
+                CHECK(all_zero(&ip, sizeof ip), "refused proof's ip_proof not zero");
+                continue;
+            }
+            CHECK(ip.n == n && ip.L_len == Lr && ip.a.length == 1 && ip.b.length == 1 && ip.L.length == Lr && ip.R.length == Lr,
+                  "lengths %zu", i);
+            CHECK(!memcmp(ip.a.elements, &o.a[i], 32) && !memcmp(ip.b.elements, &o.b[i], 32) && !memcmp(&ip.x, &o.x[i], 32),
+                  "a, b, x %zu", i);
+            if (Lr) CHECK(!memcmp(ip.L.elements, o.L + i * Lr, Lr * 128) && !memcmp(ip.R.elements, o.R + i * Lr, Lr * 128), "L, R %zu", i);
+        }
+    } else {
+        CHECK(failed >= 1, "allocation %ld failed but no fill reported it", fail_at);
+    }
+    own.rollback();
+    CHECK(g_live.empty(), "%zu vectors left after the rollback", g_live.size());
+    CHECK(all_zero(proofs.data(), B * sizeof(RangeProof)), "a struct byte is not zero after the rollback");
+    CHECK(all_zero(valid.data(), B), "a valid byte is not zero after the rollback");
+    if (with_attempts) CHECK(all_zero(attempts.data(), B), "an attempts byte is not zero after the rollback");
+    else {   // the seeded prover has no attempts: the owner never touches a buffer it was not given
+        std::vector<uint8_t> want(B);
+        pattern(want.data(), B, 7);
+        CHECK(attempts == want, "attempts written without being given");
+    }
+    own.rollback();   // a second rollback finds nothing to free
+    CHECK(g_live.empty(), "second rollback");
+}
+
+int main() {
+    plan();
+    for (size_t Lr : {size_t(0), size_t(4)})
+        for (bool att : {false, true})
+            for (long k = 0; k <= 4 * 8 + 1; k++) owner_case(Lr, att, k);
+    std::printf("%llu %llu\n", (u64)checks, (u64)fails);
+    return fails ? 1 : 0;
+}
