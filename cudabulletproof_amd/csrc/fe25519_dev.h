@@ -315,18 +315,63 @@ BP_DEV void mul512(uint64_t t[8], const fe& f, const fe& g, uint32_t* gacc = nul
 #ifndef BP_DEFER_GATES
 #define BP_DEFER_GATES 1
 #endif
+// BP_MUL_CIN 1: the throughput forms (LAT 0 and 3; fe_mul_k in ge25519_dev.h) take the products whose
+// columns read a zero-high carry-in as an operand (mul512_asm.h *_cin_asm: the same columns and bits, one
+// 64-bit register move fewer per product, three per square, five per product by k); 0 is the in-place
+// rendering, for A/B builds.  The latency forms and the quad forms (ge25519_quad.h) keep the in-place products.
+#ifndef BP_MUL_CIN
+#define BP_MUL_CIN 1
+#endif
+#if BP_MUL_CIN && BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
+// mul512 / sqr512's device paths on the *_cin_asm statements: the same gates, the same counting
+// forms on a hit.
+template <bool DEFER>
+BP_DEV void mul512_cin(uint64_t t[8], const fe& f, const fe& g, uint32_t* gacc) {
+    uint32_t a[8], b[8], w[16];
+    fe_words(a, b, f, g);
+    mul512_bounded_cin_asm(w, a, b);
+    if constexpr (DEFER) mul_gate_defer(*gacc, a[0], b[7]);
+    else if (__builtin_expect(__any(max(a[0], b[7]) > MUL_BOUNDED_WORD), 0)) mul512_asm(w, a, b);
+#pragma unroll
+    for (int i = 0; i < 8; i++) t[i] = cat64(w[2 * i], w[2 * i + 1]);
+}
+#endif
+
 template <int LAT = 0>
 BP_DEV fe fe_mul(const fe& f, const fe& g, uint32_t* acc = nullptr, uint32_t* gacc = nullptr) {
     uint64_t t[8];
+#if BP_MUL_CIN && BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LAT == 0 || LAT == 3) mul512_cin<LAT == 3 && BP_DEFER_GATES>(t, f, g, gacc); else
+#endif
     mul512<LAT == 3 && BP_DEFER_GATES>(t, f, g, gacc);
     return fe_fold512<LAT>(t, acc);
+}
+
+// The square's second half: t = 2 o + sum a_i^2 2^(64 i) from the off-diagonal half o.
+BP_DEV void sqr512_double(uint64_t t[8], const uint32_t a[8], const uint32_t o[16]) {
+    uint32_t w[16];
+    // w = 2 o + sum a_i^2 2^(64 i): one carry chain over the doubled words (funnel shifts)
+    unsigned c = 0;
+    uint64_t d0 = (uint64_t)a[0] * a[0];
+    w[0] = (uint32_t)d0;
+    w[1] = __builtin_addc(o[1] << 1, (uint32_t)(d0 >> 32), 0u, &c);
+#pragma unroll
+    for (int i = 1; i < 8; i++) {
+        uint64_t di = (uint64_t)a[i] * a[i];
+        uint32_t lo = (o[2 * i] << 1) | (o[2 * i - 1] >> 31);
+        uint32_t hi = (o[2 * i + 1] << 1) | (o[2 * i] >> 31);
+        w[2 * i] = __builtin_addc(lo, (uint32_t)di, c, &c);
+        w[2 * i + 1] = __builtin_addc(hi, (uint32_t)(di >> 32), c, &c);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) t[i] = cat64(w[2 * i], w[2 * i + 1]);
 }
 
 // Exact 512-bit square: 2 * (off-diagonal products, 28 of them) + the 8 diagonal squares —
 // the same 512 bits as mul512(t, f, f) with 36 instead of 64 32x32 products.
 template <bool DEFER = false>
 BP_DEV void sqr512(uint64_t t[8], const fe& f, uint32_t* gacc = nullptr) {
-    uint32_t a[8], o[16], w[16];
+    uint32_t a[8], o[16];
     fe_words(a, f);
 #if BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     sqr512_offdiag_bounded_asm(o, a);
@@ -353,27 +398,28 @@ BP_DEV void sqr512(uint64_t t[8], const fe& f, uint32_t* gacc = nullptr) {
     o[14] = (uint32_t)acc;
     o[15] = (uint32_t)(acc >> 32);
 #endif
-    // w = 2 o + sum a_i^2 2^(64 i): one carry chain over the doubled words (funnel shifts)
-    unsigned c = 0;
-    uint64_t d0 = (uint64_t)a[0] * a[0];
-    w[0] = (uint32_t)d0;
-    w[1] = __builtin_addc(o[1] << 1, (uint32_t)(d0 >> 32), 0u, &c);
-#pragma unroll
-    for (int i = 1; i < 8; i++) {
-        uint64_t di = (uint64_t)a[i] * a[i];
-        uint32_t lo = (o[2 * i] << 1) | (o[2 * i - 1] >> 31);
-        uint32_t hi = (o[2 * i + 1] << 1) | (o[2 * i] >> 31);
-        w[2 * i] = __builtin_addc(lo, (uint32_t)di, c, &c);
-        w[2 * i + 1] = __builtin_addc(hi, (uint32_t)(di >> 32), c, &c);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = cat64(w[2 * i], w[2 * i + 1]);
+    sqr512_double(t, a, o);
 }
 
 // fe25519_sq (curve25519_ops.cu:149) == mul(f, f): the same exact product, then the same fold.
+#if BP_MUL_CIN && BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
+template <bool DEFER>
+BP_DEV void sqr512_cin(uint64_t t[8], const fe& f, uint32_t* gacc) {
+    uint32_t a[8], o[16];
+    fe_words(a, f);
+    sqr512_offdiag_bounded_cin_asm(o, a);
+    if constexpr (DEFER) mul_gate_defer(*gacc, a[0], a[7]);
+    else if (__builtin_expect(__any(max(a[0], a[7]) > MUL_BOUNDED_WORD), 0)) sqr512_offdiag_asm(o, a);
+    sqr512_double(t, a, o);
+}
+#endif
+
 template <int LAT = 0>
 BP_DEV fe fe_sq(const fe& f, uint32_t* acc = nullptr, uint32_t* gacc = nullptr) {
     uint64_t t[8];
+#if BP_MUL_CIN && BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LAT == 0 || LAT == 3) sqr512_cin<LAT == 3 && BP_DEFER_GATES>(t, f, gacc); else
+#endif
     sqr512<LAT == 3 && BP_DEFER_GATES>(t, f, gacc);
     return fe_fold512<LAT>(t, acc);
 }

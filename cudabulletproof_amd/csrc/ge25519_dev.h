@@ -34,7 +34,7 @@ BP_DEV fe fe_mul_k(const fe& f, uint32_t* acc = nullptr) {
 #if BP_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     uint32_t a[8], w[16];
     fe_words(a, f);
-    mul512_k_asm(w, a);
+    if constexpr (BP_MUL_CIN && (LAT == 0 || LAT == 3)) mul512_k_cin_asm(w, a); else mul512_k_asm(w, a);
     uint64_t t[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) t[i] = cat64(w[2 * i], w[2 * i + 1]);

@@ -24,7 +24,7 @@ def offdiag(k):
     return [(i, k - i) for i in range(8) if i < k - i <= 7]
 
 
-def emit_column(k, prods=None, first=None, bounded=False):
+def emit_column(k, prods=None, first=None, bounded=False, cin=False):
     """One product-scanning column as asm lines.  bounded (an int, True = 1): that many leading
     products of the column cannot carry out of the 64-bit accumulator (the caller has checked the
     operand words that bound them, see BOUNDED below), so only the later products' carries are
@@ -55,6 +55,8 @@ def emit_column(k, prods=None, first=None, bounded=False):
             _, i, j, sname, t = op
             if first and t == 0:
                 lines.append(f"v_mad_u64_u32 %[acc], %[{sname}], %[a{i}], %[b{j}], 0")
+            elif cin and t == 0:
+                lines.append(f"v_mad_u64_u32 %[acc], %[{sname}], %[a{i}], %[b{j}], %[cin]")
             else:
                 lines.append(f"v_mad_u64_u32 %[acc], %[{sname}], %[a{i}], %[b{j}], %[acc]")
             if sname != "sd":
@@ -122,18 +124,26 @@ def k_columns(rows=8):
 
 
 def emit_product(out, fname, sig, wname, cols, last, bounded=False, square=False, pre=(), uncounted=None,
-                 bconst=None):
+                 bconst=None, split_cin=False):
     """One generated product function.  cols = [(k, prods, first)]: column k's words go to
     wname[k]; `last` = the index of the final carry word (wname[last] = the accumulator's high part).
-    square: operand b is a (the off-diagonal half of a square)."""
+    square: operand b is a (the off-diagonal half of a square).
+    split_cin: a column that follows one with no counted carry takes its carry-in (acc >> 32, high
+    word zero) as an input operand and writes a fresh accumulator.  In place ("+v"), the compiler builds
+    that pair beside a shared zero register and then copies it into the accumulator with a v_mov_b64;
+    as an input the built pair is read where it stands (one v_mov_b32, no 64-bit move)."""
     out.append(f"__device__ __forceinline__ void {fname}({sig}) {{")
-    out.append("    uint64_t acc = 0, s0, s1, s2, sd;")
+    out.append("    uint64_t acc = 0, s0, s1, s2, sd;" if not split_cin else "    uint64_t acc = 0, cin, s0, s1, s2, sd;")
     out.append("    uint32_t c2;")
     out.extend(pre)
     prev_counted = 0
     for idx, (k, prods, first) in enumerate(cols):
-        _, lines, counted = emit_column(k, prods, first=first, bounded=uncounted(k) if uncounted else bounded)
-        if idx > 0:   # the previous column's carry-out: (acc >> 32) + 2^32 (its counted carries)
+        split = split_cin and idx > 0 and not prev_counted
+        _, lines, counted = emit_column(k, prods, first=first, bounded=uncounted(k) if uncounted else bounded,
+                                        cin=split)
+        if split:
+            out.append("    cin = acc >> 32;")
+        elif idx > 0:   # the previous column's carry-out: (acc >> 32) + 2^32 (its counted carries)
             out.append("    acc = (acc >> 32) | ((uint64_t)c2 << 32);" if prev_counted else "    acc >>= 32;")
         ai = sorted({i for i, _ in prods} | ({j for _, j in prods} if square else set()))
         bj = [] if square else sorted({j for _, j in prods})
@@ -144,6 +154,12 @@ def emit_product(out, fname, sig, wname, cols, last, bounded=False, square=False
         ops_in = ", ".join([f'[a{i}] "v"(a[{i}])' for i in ai] + [bop(j) for j in bj])
         if first:
             out.append(f'    asm volatile("{body}" : [acc] "=&v"(acc), [s0] "=&s"(s0) : {ops_in});')
+        elif split:
+            c2_out = '[c2] "=&v"(c2), ' if counted else ""
+            out.append(f'    asm volatile("{body}"')
+            out.append(f'                 : [acc] "=&v"(acc), {c2_out}[s0] "=&s"(s0), [s1] "=&s"(s1), '
+                       f'[s2] "=&s"(s2), [sd] "=&s"(sd)')
+            out.append(f'                 : {ops_in}, [cin] "v"(cin));')
         elif counted:
             out.append(f'    asm volatile("{body}"')
             out.append(f'                 : [acc] "+v"(acc), [c2] "=&v"(c2), [s0] "=&s"(s0), [s1] "=&s"(s1), '
@@ -160,7 +176,7 @@ def emit_product(out, fname, sig, wname, cols, last, bounded=False, square=False
     out.append(f"    {wname}[{last}] = (uint32_t)acc;")
     if square:
         out.append(f"    {wname}[{last + 1}] = (uint32_t)(acc >> 32);")
-    out.append("    (void)s0; (void)s1; (void)s2; (void)sd; (void)c2;")
+    out.append("    (void)s0; (void)s1; (void)s2; (void)sd; (void)c2;" + (" (void)cin;" if split_cin else ""))
     out.append("}")
     out.append("")
 
@@ -208,6 +224,15 @@ def main(path=OUT):
     emit_product(out, "mul512_k_asm", "uint32_t w[16], const uint32_t a[8]", "w",
                  [(k, prods, first) for k, prods, first, _ in kcols], 15, uncounted=lambda k: unc[k],
                  bconst="kw", pre=(f"    constexpr uint32_t kw[8] = {{{kw}}};",))
+    out.append("// The products of fe25519_dev.h BP_MUL_CIN (the lane forms): the same columns, a column after one with no")
+    out.append("// counted carry taking its carry-in as an operand of its own (emit_product split_cin): no 64-bit move.")
+    emit_product(out, "mul512_bounded_cin_asm", "uint32_t w[16], const uint32_t a[8], const uint32_t b[8]", "w", full,
+                 15, bounded=True, split_cin=True)
+    emit_product(out, "sqr512_offdiag_bounded_cin_asm", "uint32_t o[16], const uint32_t a[8]", "o", off, 14,
+                 bounded=True, square=True, pre=("    o[0] = 0;",), split_cin=True)
+    emit_product(out, "mul512_k_cin_asm", "uint32_t w[16], const uint32_t a[8]", "w",
+                 [(k, prods, first) for k, prods, first, _ in kcols], 15, uncounted=lambda k: unc[k],
+                 bconst="kw", pre=(f"    constexpr uint32_t kw[8] = {{{kw}}};",), split_cin=True)
     kcols2, kcount2 = k_columns(2)
     out.append(f"// A lane's two rows of fe_mul_q4(x, k): (a1 2^32 + a0) * k as 10 words, {kcount2} carries counted (the")
     out.append(f"// bounded general rows count 7).")
