@@ -24,7 +24,7 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libcudabulletproof_hip.so")
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["bp_terms1.hip", "bp_terms2.hip", "bp_terms4.hip", "bp_terms16.hip", "bp_kernels.hip", "bp_prove.hip",
-           "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_capi.hip"]
+           "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_commit.hip", "bp_capi.hip"]
 
 _lib = None
 
@@ -131,6 +131,8 @@ EXPORTS = [
     "hipbp_batch_generate_range_proof_accepted", "hipbp_batch_generate_range_proof_accepted_gens",
     "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats",
     "hipbp_batch_generate_range_proof_host_sharded", "hipbp_batch_generate_range_proof_accepted_host",
+    "hipbp_batch_pedersen_commit", "hipbp_batch_pedersen_commit_gens", "hipbp_batch_pedersen_open",
+    "hipbp_batch_pedersen_commit_host",
 ]
 
 
@@ -163,7 +165,9 @@ def lib():
                   "hipbp_batch_generate_range_proof_seeded_gens", "hipbp_batch_generate_range_proof_host",
                   "hipbp_batch_generate_range_proof_accepted", "hipbp_batch_generate_range_proof_accepted_gens",
                   "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats",
-                  "hipbp_batch_generate_range_proof_host_sharded", "hipbp_batch_generate_range_proof_accepted_host"):
+                  "hipbp_batch_generate_range_proof_host_sharded", "hipbp_batch_generate_range_proof_accepted_host",
+                  "hipbp_batch_pedersen_commit", "hipbp_batch_pedersen_commit_gens", "hipbp_batch_pedersen_open",
+                  "hipbp_batch_pedersen_commit_host"):
             getattr(L, f).restype = ctypes.c_int
         _lib = L
     return _lib
@@ -712,6 +716,83 @@ def batch_generate_range_proof_accepted_host(v, gamma, n, G, H, g, h, seed, inde
     return _take_proofs(arr, count), valid[:count].astype(bool), attempts[:count].copy()
 
 
+# ---------------------------------------------------------------------- Pedersen commitments
+def _commit_args(v, gamma, g, h, gens):
+    """(count, [v, gamma, g, h] contiguous; g, h None with a generator set) of a commit / open call."""
+    if gens is None and (g is None or h is None):
+        raise ValueError("g and h are needed without a generator set")
+    ins = [v.contiguous(), gamma.contiguous()] + [None if gens is not None else t.contiguous() for t in (g, h)]
+    count = int(ins[0].numel() // 4)
+    if ins[0].numel() != count * 4 or ins[1].numel() != count * 4:
+        raise ValueError("v and gamma must both be (count, 4)")
+    return count, ins
+
+
+def batch_pedersen_commit(v, gamma, g, h, out=None, stream=None, gens=None):
+    """pedersen_commit (bulletproof_range_proof.cu:277) over a batch, on the GPU
+    (hipbp_batch_pedersen_commit): out[i] = N(add(N(sm(tobytes(v[i]), g)), N(sm(tobytes(gamma[i]), h)))),
+    the V batch_generate_range_proof gives where valid = 1, without its range check.
+
+    v, gamma (count,4); g, h (16,): int64 CUDA tensors of the u64 limbs.  gens= a Generators set (any
+    n): its g, h and prefix tables are used (g, h are not read and may be None); the same bits.
+    out: a (count,16) int64 CUDA tensor to write (it must not overlap the inputs), or None for a new
+    one.  Asynchronous on `stream`.  Returns the (count,16) tensor."""
+    import contextlib
+
+    import torch
+    count, ins = _commit_args(v, gamma, g, h, gens)
+    if out is None:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            out = torch.empty(count, 16, dtype=torch.int64, device=v.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (count, 16) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous ({count}, 16) int64 tensor")
+    if gens is not None:
+        _chk(lib().hipbp_batch_pedersen_commit_gens(_c(out.data_ptr()), _c(ins[0].data_ptr()), _c(ins[1].data_ptr()),
+                                                    _sz(count), _c(gens.h), _stream_ptr(stream)))
+    else:
+        _chk(lib().hipbp_batch_pedersen_commit(_c(out.data_ptr()), _c(ins[0].data_ptr()), _c(ins[1].data_ptr()),
+                                               _sz(count), _c(ins[2].data_ptr()), _c(ins[3].data_ptr()),
+                                               _stream_ptr(stream)))
+    return out
+
+
+def batch_pedersen_open(V, v, gamma, g, h, stream=None, gens=None):
+    """hipbp_batch_pedersen_open: ok[i] = 1 iff all 16 limbs of V[i] equal batch_pedersen_commit's
+    commitment of (v[i], gamma[i]).  V (count,16), v, gamma (count,4), g, h (16,) int64 CUDA tensors;
+    gens= as in batch_pedersen_commit.  Asynchronous on `stream`.  Returns a (count,) uint8 CUDA tensor."""
+    import contextlib
+
+    import torch
+    count, ins = _commit_args(v, gamma, g, h, gens)
+    V = V.contiguous()
+    if V.numel() != count * 16:
+        raise ValueError(f"V must be ({count}, 16)")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        ok = torch.empty(count, dtype=torch.uint8, device=v.device)
+    _chk(lib().hipbp_batch_pedersen_open(_c(ok.data_ptr()), _c(V.data_ptr()), _c(ins[0].data_ptr()),
+                                         _c(ins[1].data_ptr()), _sz(count),
+                                         _c(ins[2].data_ptr()) if ins[2] is not None else None,
+                                         _c(ins[3].data_ptr()) if ins[3] is not None else None,
+                                         _c(gens.h) if gens is not None else None, _stream_ptr(stream)))
+    return ok
+
+
+def batch_pedersen_commit_host(v, gamma, g, h, num_gpus=1):
+    """hipbp_batch_pedersen_commit_host: batch_pedersen_commit on host arrays.  v, gamma (count,4),
+    g, h (16,) uint64; returns a (count,16) uint64 array with the device call's bytes.  Synchronous.
+    num_gpus: the devices the batch is split over, from the current one on (1: the current device
+    alone; 0: all visible); the result does not depend on it."""
+    require_gpu()
+    v, gamma = _u64(v, 4).reshape(-1, 4), _u64(gamma, 4).reshape(-1, 4)
+    if len(v) != len(gamma):
+        raise ValueError("v and gamma must have the same length")
+    g, h = _u64(g, 16), _u64(h, 16)
+    out = np.zeros((len(v), 16), np.uint64)
+    _chk(lib().hipbp_batch_pedersen_commit_host(_p(out), _p(v), _p(gamma), _sz(len(v)), _p(g), _p(h),
+                                                ctypes.c_int(num_gpus)))
+    return out
+
+
 def batch_inner_product_prove(n, a, b, c, G, H, Q, transcript=None, stream=None, gens=None):
     """inner_product_prove (bulletproof_vectors.cu:277) over a batch, on the GPU, for any power-of-two
     n up to 65536 (hipbp_batch_inner_product_prove).
@@ -855,7 +936,7 @@ def msm_pippenger_horner(results, window_sums, window_bits=12, stream=None):
 
 def release_stream_workspaces(stream=None):
     """hipbp_release_stream_workspaces: free every workspace cached for `stream` on the current
-    device (MSM, prover, one-shot pipelines, Pippenger pair); call before dropping a stream."""
+    device (MSM, prover, commitments, one-shot pipelines, Pippenger pair); call before dropping a stream."""
     _chk(lib().hipbp_release_stream_workspaces(_stream_ptr(stream)))
 
 

@@ -130,6 +130,7 @@ struct StreamWs {
     hipStream_t ipa_side = nullptr;
     hipEvent_t ipa_ev[2] = {};   // [0] the caller's stream at entry, [1] the side stream's last chunk done
     bp::PipPair pip;             // Pippenger MSM (hipbp_msm_pippenger*): both parts' buffers and its side stream
+    Buf commit[bp::CB_COUNT];    // Pedersen commitments (hipbp_batch_pedersen_commit*): one chunk's terms
     std::map<std::pair<int, int>, Pipeline*> pipes;   // one-shot verify pipelines, per (n, mode)
     hipError_t release(hipError_t first);
 };
@@ -570,6 +571,7 @@ hipError_t StreamWs::release(hipError_t first) {
     keep(seed_scal.release());
     for (auto& b : accept) keep(b.release());
     keep(accept_cnt.release());
+    for (auto& b : commit) keep(b.release());
     if (ipa_side) keep(hipStreamSynchronize(ipa_side));
     for (auto& half : ipa)
         for (auto& b : half) keep(b.release());
@@ -877,7 +879,8 @@ int hipbp_msm_pippenger_windows(ge25519* window_sums, const fe25519* scalars, co
 }
 
 // Frees every per-stream workspace the engine keeps for `stream` on the current device (canonical
-// MSM / point-tree buffers, prover buffers, IPA prover pair, Pippenger pair, one-shot verify pipelines):
+// MSM / point-tree buffers, prover buffers, commitment terms, IPA prover pair, Pippenger pair, one-shot
+// verify pipelines):
 // the stream's one record, after waiting for the stream (and, in the record's release, for the two
 // pairs' side streams).  A later call on that stream builds them again.
 int hipbp_release_stream_workspaces(void* stream) {
@@ -1675,6 +1678,149 @@ int hipbp_batch_generate_range_proof_accepted_host(RangeProof* proofs, uint8_t* 
                                                    int max_attempts, int check, int num_gpus) {
     return prove_host_run(proofs, valid, attempts, v, gamma, count, n, G, H, g, h, seed32, index_base, true,
                           max_attempts, check, num_gpus);
+}
+
+// ---- Pedersen commitments (bp_commit.hip): pedersen_commit over a batch.  commit_run enqueues a whole
+// call on `s`: chunks of HIPBP_COMMIT_CHUNK commitments (read at every call; bp::commit_chunk), one
+// after another through the stream's one commit workspace (a chunk's launches are ordered behind the
+// previous chunk's on the stream, so the terms are never overwritten while still read).  V null:
+// out[i] = the commitment; else ok[i] = (V[i] == the commitment).
+static int commit_run(Engine& e, ge25519* out, uint8_t* ok, const ge25519* V, const fe25519* v, const fe25519* gamma,
+                      size_t count, const bp::ge* g, const bp::ge* h, const bp::ge* ptab, int pbits, size_t gens_n,
+                      hipStream_t s) {
+    using namespace bp;   // the table's ids and types
+    const char* ce = getenv("HIPBP_COMMIT_CHUNK");
+    const size_t chunk = commit_chunk(count, ce ? atoll(ce) : 0);
+    std::lock_guard<std::mutex> lk(e.mu);
+    Buf(&b)[CB_COUNT] = e.streams[s].commit;
+    size_t sz[CB_COUNT];
+    // the chain-length sort of each class's lanes (HIPBP_COMMIT_SORT, read at every call)
+    const bool sort = commit_sorted(chunk, getenv("HIPBP_COMMIT_SORT"));
+    commit_sizes(chunk, sort, sz);
+    for (int k = 0; k < CB_COUNT; k++)   // nothing queued on `s` reads a buffer that grows
+        if (sz[k] > b[k].cap && b[k].p) { BP_RET_ON(hipStreamSynchronize(s)); break; }
+    BP_RET_ON(need_all(b, sz));
+    CommitWs w{};
+    BP_COMMIT_BUFS(BP_BUF_FIELD)
+    if (!sort) { w.order = nullptr; w.bins = nullptr; }   // (a sorted call may have left them allocated)
+    for (size_t c0 = 0; c0 < count; c0 += chunk) {
+        const size_t c = std::min(chunk, count - c0);
+        const CommitIn in{c, (const fe*)v + c0, (const fe*)gamma + c0, g, h, ptab, ptab ? pbits : 0, (int)gens_n};
+        launch_commit(in, w, out ? (ge*)out + c0 : nullptr, V ? (const ge*)V + c0 : nullptr, ok ? ok + c0 : nullptr,
+                      e.dtab, s);
+    }
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_batch_pedersen_commit(ge25519* out, const fe25519* v, const fe25519* gamma, size_t count, const ge25519* g,
+                                const ge25519* h, void* stream) {
+    BP_ENGINE_OR_RET(e);
+    if (count == 0) return HIPBP_OK;
+    if (!out || !v || !gamma || !g || !h) { g_err = "null argument"; return HIPBP_ERR_ARG; }
+    return commit_run(*e, out, nullptr, nullptr, v, gamma, count, (const bp::ge*)g, (const bp::ge*)h, nullptr, 0, 0,
+                      pick(stream));
+}
+
+int hipbp_batch_pedersen_commit_gens(ge25519* out, const fe25519* v, const fe25519* gamma, size_t count, void* gens,
+                                     void* stream) {
+    BP_ENGINE_OR_RET(e);
+    const Gens* gs = (const Gens*)gens;
+    if (int rc = gens_check(gs, 0, nullptr)) return rc;
+    if (count == 0) return HIPBP_OK;
+    if (!out || !v || !gamma) { g_err = "null argument"; return HIPBP_ERR_ARG; }
+    return commit_run(*e, out, nullptr, nullptr, v, gamma, count, gs->g(), gs->h(),
+                      gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits, gs->n, pick(stream));
+}
+
+int hipbp_batch_pedersen_open(uint8_t* ok, const ge25519* V, const fe25519* v, const fe25519* gamma, size_t count,
+                              const ge25519* g, const ge25519* h, void* gens, void* stream) {
+    BP_ENGINE_OR_RET(e);
+    const Gens* gs = (const Gens*)gens;
+    if (gs)
+        if (int rc = gens_check(gs, 0, nullptr)) return rc;
+    if (count == 0) return HIPBP_OK;
+    if (!ok || !V || !v || !gamma || (!gs && (!g || !h))) { g_err = "null argument"; return HIPBP_ERR_ARG; }
+    if (gs)
+        return commit_run(*e, nullptr, ok, V, v, gamma, count, gs->g(), gs->h(),
+                          gs->bits ? gs->tab.as<bp::ge>() : nullptr, gs->bits, gs->n, pick(stream));
+    return commit_run(*e, nullptr, ok, V, v, gamma, count, (const bp::ge*)g, (const bp::ge*)h, nullptr, 0, 0,
+                      pick(stream));
+}
+
+// One shard of the host form on device `dev`: commitments [lo, hi) of the call, in pieces of one
+// commit chunk through the device's prove-host staging (v | gamma | g | h | out of a piece; the
+// shard keeps prove_host_mu like the host provers' shards, so shards and calls that share a device
+// run one after another) on the engine's own stream, each piece drained before the next is staged.
+static int commit_host_shard(int dev, ge25519* out, const fe25519* v, const fe25519* gamma, size_t lo, size_t hi,
+                             const ge25519* g, const ge25519* h) {
+    BP_RET_ON(hipSetDevice(dev));
+    BP_ENGINE_OR_RET(e);
+    std::unique_lock<std::mutex> hold(e->prove_host_mu);
+    const size_t FE = bp::FE, GE = bp::GE;
+    const char* ce = getenv("HIPBP_COMMIT_CHUNK");
+    const size_t piece = bp::commit_chunk(hi - lo, ce ? atoll(ce) : 0);
+    hipStream_t s = e->stream;
+    BP_RET_ON(hipStreamSynchronize(s));   // (the staging may grow)
+    BP_RET_ON(e->prove_host_dev.need(2 * GE + piece * (2 * FE + GE)));
+    uint8_t* d = e->prove_host_dev.as<uint8_t>();
+    const bp::ge* dg = (const bp::ge*)d;
+    const fe25519* dv = (const fe25519*)(d + 2 * GE);
+    ge25519* dout = (ge25519*)(d + 2 * GE + 2 * piece * FE);
+    BP_RET_ON(hipMemcpyAsync(d, g, GE, hipMemcpyHostToDevice, s));
+    BP_RET_ON(hipMemcpyAsync(d + GE, h, GE, hipMemcpyHostToDevice, s));
+    for (size_t c0 = lo; c0 < hi; c0 += piece) {
+        const size_t c = std::min(piece, hi - c0);
+        BP_RET_ON(hipMemcpyAsync((void*)dv, v + c0, c * FE, hipMemcpyHostToDevice, s));
+        BP_RET_ON(hipMemcpyAsync((void*)(dv + piece), gamma + c0, c * FE, hipMemcpyHostToDevice, s));
+        if (int rc = commit_run(*e, dout, nullptr, nullptr, dv, dv + piece, c, dg, dg + 1, nullptr, 0, 0, s)) return rc;
+        BP_RET_ON(hipMemcpyAsync(out + c0, dout, c * GE, hipMemcpyDeviceToHost, s));
+        BP_RET_ON(hipStreamSynchronize(s));
+    }
+    return HIPBP_OK;
+}
+
+int hipbp_batch_pedersen_commit_host(ge25519* out, const fe25519* v, const fe25519* gamma, size_t count,
+                                     const ge25519* g, const ge25519* h, int num_gpus) {
+    if (count == 0) return HIPBP_OK;
+    if (!out || !v || !gamma || !g || !h) { g_err = "null argument"; return HIPBP_ERR_ARG; }
+    int ndev = 0;
+    BP_RET_ON(hipGetDeviceCount(&ndev));
+    if (ndev <= 0) { g_err = "no HIP device"; return HIPBP_ERR_DEVICE; }
+    if (num_gpus > ndev) {   // hipbp_batch_range_proof_verify_host's rule and message
+        g_err = "num_gpus = " + std::to_string(num_gpus) + " but " + std::to_string(ndev) + " HIP device(s) visible";
+        return HIPBP_ERR_ARG;
+    }
+    int ng = num_gpus <= 0 ? ndev : num_gpus;
+    if (num_gpus <= 0)   // HIPBP_HOST_SHARDS=k, as the host provers read it
+        if (const char* hs = getenv("HIPBP_HOST_SHARDS"))
+            if (atoi(hs) > 0) ng = (int)std::min<size_t>(std::min(atoi(hs), 64), count);
+    int dev0 = 0;   // shard d runs on device (dev0 + d) % ndev: num_gpus = 1 stays on the caller's
+    BP_RET_ON(hipGetDevice(&dev0));
+    const std::vector<bp::HostShard> shards = bp::plan_host_shards(count, ng);   // the host provers' split
+    const size_t ns = shards.size();
+    std::vector<int> rcs(ns, HIPBP_OK);
+    std::vector<std::string> errs(ns);
+    auto run_shard = [&](size_t k) {
+        const bp::HostShard& sh = shards[k];
+        rcs[k] = commit_host_shard((dev0 + sh.d) % ndev, out, v, gamma, sh.lo, sh.hi, g, h);
+        if (rcs[k] != HIPBP_OK) errs[k] = g_err;   // g_err is per thread
+    };
+    if (ns == 1 && shards[0].d == 0) {
+        run_shard(0);
+    } else {
+        std::vector<std::thread> workers;
+        for (size_t k = 0; k < ns; k++) workers.emplace_back(run_shard, k);
+        for (auto& w : workers) w.join();
+    }
+    for (size_t k = 0; k < ns; k++)   // the first failure in shard order, every thread joined
+        if (rcs[k] != HIPBP_OK) {
+            g_err = "device " + std::to_string(shards[k].d) + ": " + errs[k];
+            (void)hipSetDevice(dev0);
+            return rcs[k];
+        }
+    BP_RET_ON(hipSetDevice(dev0));
+    return HIPBP_OK;
 }
 
 // ---- stand-alone IPA prover (bp_ipa_prove.hip).  The engine's lock is held by the caller.

@@ -347,6 +347,42 @@ void launch_ipa_round(const IpaWs& ws, int r, const ge* G, const ge* H, const ge
 void launch_ipa_final(const IpaWs& ws, const fe* c_in, fe* a, fe* b, fe* c, fe* x, fe* c_final /* nullable */,
                       hipStream_t s);
 
+// ------------------------------------------------------------------ Pedersen commitments (bp_commit.hip)
+// One chunk of pedersen_commit calls (hipbp_batch_pedersen_commit): count commitments of (v, gamma)
+// on the bases g, h.
+struct CommitIn {
+    size_t count;
+    const fe* v;       // [count] values (any four limbs)
+    const fe* gamma;   // [count] blindings
+    const ge* g;
+    const ge* h;
+    // fixed-base prefix tables of a generator set of n (nullable; the SlotDev::ptab layout: row 2n is
+    // h's, row 2n + 1 g's)
+    const ge* ptab;
+    int pbits, n;
+};
+struct CommitWs {
+    ge* terms;         // [2*count] N(sm(v, g)) at [0, count), N(sm(gamma, h)) at [count, 2 count)
+    // the chain-length sort (nullable: index order): order[k] at [0, count) the blinding class's lane
+    // order, at [count, 2 count) the value class's, each longest chain first; bins: the two classes'
+    // counting-sort bins
+    uint32_t* order;   // [2*count]
+    unsigned* bins;    // [2*MSM_BINS]
+};
+// Lanes of one class of k_commit_terms' grid (blinding terms, then value terms): whole waves.
+__host__ __device__ inline size_t commit_class_lanes(size_t count) { return (count + 63) & ~(size_t)63; }
+// Lane -> its item: `val` the class (false: blinding term, true: value term), the commitment's index
+// returned, or SIZE_MAX for a padding lane.  The class is constant over every aligned 64 lanes.
+__host__ __device__ inline size_t commit_lane_item(size_t count, size_t lane, bool& val) {
+    const size_t P = commit_class_lanes(count);
+    val = lane >= P;
+    const size_t j = val ? lane - P : lane;
+    return j < count ? j : SIZE_MAX;
+}
+// V null: out[i] = the commitment; else ok[i] = (V[i] == the commitment, all 16 limbs), out unread
+void launch_commit(const CommitIn& in, const CommitWs& ws, ge* out, const ge* V, uint8_t* ok, const ge* dtab,
+                   hipStream_t s);
+
 // Elementwise field ops: op 0 add, 1 sub, 2 mul, 3 square-kernel quirk, 4 soa add (limbwise, no carry)
 void launch_field_op(int op, fe* r, const fe* a, const fe* b, size_t count, hipStream_t s);
 void launch_sha_probe(int kind, fe* out, const fe* in, size_t count, hipStream_t s);

@@ -222,6 +222,31 @@ inline void ipa_sizes(size_t Bc, size_t n, size_t (&sz)[IB_COUNT]) {
     BP_IPA_BUFS(BP_BUF_SIZE)
 }
 
+// One chunk of Pedersen commitments (CommitWs): c commitments, two scalar-mult terms each.  order,
+// bins: with the chain-length sort only (HIPBP_COMMIT_SORT).
+#define BP_COMMIT_BUFS(X)                                  \
+    X(CB_TERMS, terms, ge, 2 * c * GE)                     \
+    X(CB_ORDER, order, uint32_t, sort ? 2 * c * U32 : 0)   \
+    X(CB_BINS, bins, unsigned, sort ? 2 * MSM_BINS * U32 : 0)
+enum CommitBuf { BP_COMMIT_BUFS(BP_BUF_ID) CB_COUNT };
+constexpr size_t COMMIT_CHUNK = (size_t)1 << 20;       // HIPBP_COMMIT_CHUNK's default: 256 MB of terms
+constexpr size_t COMMIT_CHUNK_MAX = (size_t)1 << 24;   // ... and its limit (the grid stays under 2^31 lanes)
+// HIPBP_COMMIT_SORT unset: chunks of at least this many commitments are sorted (MSM_SORT_MIN's rule: below
+// it the waves all run at once and the order cannot shorten the launch, while the sort's five small
+// launches add ~0.25 ms to a 1.6 ms call); 1: every chunk; 0: none
+constexpr size_t COMMIT_SORT_MIN = 4096;
+inline bool commit_sorted(size_t chunk, const char* env) { return env ? atoi(env) != 0 : chunk >= COMMIT_SORT_MIN; }
+inline void commit_sizes(size_t c, bool sort, size_t (&sz)[CB_COUNT]) {
+    BP_COMMIT_BUFS(BP_BUF_SIZE)
+}
+// The chunk a call of `count` commitments runs in: `env` is HIPBP_COMMIT_CHUNK's value (0: unset or
+// not positive), clamped to COMMIT_CHUNK_MAX, and never more than count itself.
+inline size_t commit_chunk(size_t count, long long env) {
+    size_t ch = env > 0 ? (size_t)env : COMMIT_CHUNK;
+    if (ch > COMMIT_CHUNK_MAX) ch = COMMIT_CHUNK_MAX;
+    return count < ch ? count : ch;
+}
+
 // A verify slot (VerifyWs) for B proofs of n bits with Lb fold rounds; Lc = max(Lb, 1); m2 = B in mode 2
 // (range_proof_verify), whose buffers the other modes leave unallocated.  B_PERM, the lane orders,
 // is no VerifyWs field: the batch's sort sets size it.

@@ -392,6 +392,57 @@ int hipbp_batch_generate_range_proof_accepted_host(RangeProof* proofs, uint8_t* 
                                                    const ge25519* h, const uint8_t seed32[32], uint64_t index_base,
                                                    int max_attempts, int check, int num_gpus);
 
+/* ---- Pedersen commitments: pedersen_commit (bulletproof_range_proof.h:28,
+ * bulletproof_range_proof.cu:277-296) over a batch, bit-exact.  With N the reference's host
+ * ge25519_normalize, sm its ge25519_scalarmult over all 256 bits and tobytes its host,
+ * canonicalising fe25519_tobytes, for every i < count
+ *     out[i] = N( add( N(sm(tobytes(v[i]), g)), N(sm(tobytes(gamma[i]), h)) ) ):
+ * the V that hipbp_batch_generate_range_proof writes for the same (v, gamma, g, h) where valid = 1.
+ * Unlike the prover there is no validate_range_input: any four limbs are a value, any four a
+ * blinding.  g and h are taken as given (Z != 1, T != X Y, limbs >= p), as everywhere in this
+ * library, and a zero scalar gives the reference's 256 doublings of the identity, normalized.
+ * One lane per scalar multiplication, the blinding terms and the value terms in waves of their own
+ * (a 64-bit value's chain is about a quarter of a blinding's, and within each class the lanes are
+ * ordered by chain length, longest first, in chunks of 4096 commitments or more; HIPBP_COMMIT_SORT,
+ * read at every call: 0 never, 1 in every chunk; the bits are the same), then one lane per
+ * commitment.  The
+ * path is for batches: a handful of commitments is faster through the reference's CPU function
+ * (DESIGN §16 records the crossover).  Large counts run in chunks of HIPBP_COMMIT_CHUNK commitments
+ * (read at every call; default 2^20, which makes 256 MB of terms; at most 2^24) one after another
+ * on `stream` through the stream's commit workspace, which grows to the largest chunk seen and is
+ * freed by hipbp_release_stream_workspaces; count itself is not bounded.
+ * All pointers DEVICE memory; asynchronous on `stream`; out must not overlap the inputs.  count = 0
+ * returns HIPBP_OK and writes nothing.  A null pointer gives HIPBP_ERR_ARG, writes nothing and
+ * enqueues nothing; a HIP error gives HIPBP_ERR_DEVICE with hipbp_last_error. */
+int hipbp_batch_pedersen_commit(ge25519* out, const fe25519* v, const fe25519* gamma, size_t count, const ge25519* g,
+                                const ge25519* h, void* stream);
+/* The same with the g and h of a generator set (hipbp_gens_create; any n) and, where the set has
+ * prefix tables, the scalar multiplications started from them (the blinding term from row 2n, the
+ * value term from row 2n + 1, for a scalar with fewer than `prefix_bits` leading zeros): the same
+ * bits.  A null gens, or one created on another device, gives HIPBP_ERR_ARG. */
+int hipbp_batch_pedersen_commit_gens(ge25519* out, const fe25519* v, const fe25519* gamma, size_t count, void* gens,
+                                     void* stream);
+/* Checks openings: ok[i] (DEVICE, [count]) = 1 iff all 16 limbs of V[i] equal the commitment of
+ * (v[i], gamma[i]) as hipbp_batch_pedersen_commit gives it, else 0: a compare of the stored limbs,
+ * not of the points they stand for, so a V that is the same point in other coordinates gives 0.
+ * gens NULL: g and h are used; gens non-NULL: the set's g, h and tables, and g, h are ignored (they
+ * may be NULL).  Nothing but ok is written.  Errors as above. */
+int hipbp_batch_pedersen_open(uint8_t* ok, const ge25519* V, const fe25519* v, const fe25519* gamma, size_t count,
+                              const ge25519* g, const ge25519* h, void* gens, void* stream);
+/* hipbp_batch_pedersen_commit on host data: HOST pointers (g, h single points), synchronous, the
+ * same bytes.  The call is split into contiguous blocks over num_gpus devices exactly as
+ * hipbp_batch_generate_range_proof_host_sharded splits: num_gpus <= 0 all visible devices; more than
+ * are visible HIPBP_ERR_ARG ("num_gpus = K but N HIP device(s) visible"), nothing written; shard d
+ * takes [count d / ng, count (d + 1) / ng) on device (current + d) mod the device count in a host
+ * thread of its own (a call of one shard runs on the caller's thread); HIPBP_HOST_SHARDS=k is read
+ * the same way; the caller's current device is restored on return.  A shard goes through in pieces
+ * of one commit chunk, each copied up, committed and copied back on the engine's stream.  No prefix
+ * tables.  count = 0 returns HIPBP_OK; a null pointer gives HIPBP_ERR_ARG and writes nothing; a
+ * failure in any shard is reported as "device d: ..." after every thread was joined (out may then
+ * hold the blocks that finished). */
+int hipbp_batch_pedersen_commit_host(ge25519* out, const fe25519* v, const fe25519* gamma, size_t count,
+                                     const ge25519* g, const ge25519* h, int num_gpus);
+
 /* ---- prover: the stand-alone inner_product_prove (bulletproof_vectors.h:94,
  * bulletproof_vectors.cu:277-523) for any power-of-two length, batched, bit-exact: the reference's
  * sequential MSM chains and inner products in its order, the ORIGINAL G, H in every round, Q any
@@ -512,7 +563,7 @@ int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, voi
  * gated forms); the results are the same bits either way.  For tests. */
 int hipbp_sm_probe(int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count, void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
- * point-tree, prover, the seeded prover's scalars and keys, the accepted prover's retry workspace, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
+ * point-tree, prover, the Pedersen commitments' terms, the seeded prover's scalars and keys, the accepted prover's retry workspace, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
  * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
  * a caller that makes short-lived streams calls this before destroying one.  No reference
  * counterpart. */
