@@ -143,8 +143,9 @@ __global__ __launch_bounds__(TPB) void k_ipa_scatter(IpaWs ws, int np, const ge*
 // item k of proof p: a_L_j G[n'+j] | b_R_j H[j] | a_R_j G[j] | b_L_j H[n'+j] (host-normalized MSM terms,
 // vectors.cu:204-206) | c_L Q | c_R Q (raw, :402-404, :435-437).  G, H are the ORIGINAL generators in
 // every round.  Grid-stride over the queued items (heavy in chain-length order, then light), one
-// scalar-mult call site (two in one wave would run both loops back to back).
-__global__ __launch_bounds__(TPB, 3) void k_ipa_terms(IpaWs ws, int np, const ge* __restrict__ G,
+// scalar-mult call site (two in one wave would run both loops back to back).  Bounded to 4 waves per SIMD
+// (128 VGPRs): with the voted lane step a 3-wave bound lets the allocator take 136 and lose the fourth wave.
+__global__ __launch_bounds__(TPB, 4) void k_ipa_terms(IpaWs ws, int np, const ge* __restrict__ G,
                                                    const ge* __restrict__ H, const ge* __restrict__ Q,
                                                    const ge* __restrict__ dtab) {
     __shared__ geq qs[TPB];

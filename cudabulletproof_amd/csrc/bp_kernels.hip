@@ -37,8 +37,8 @@ __global__ __launch_bounds__(TPB) void k_prefix_tables(ge* tab, const ge* __rest
     const geq q = ge_prep(*P);
     ge r = ge_zero();
     for (int j = K - 1; j >= 0; j--) {
-        r = ge_add_sel<false>(r, &q, false);
-        if ((p >> j) & 1) r = ge_add_sel<false>(r, &q, true);
+        r = ge_add_sel<false, false, 2>(r, &q, false);   // (PATH 2: the selected stage 1, no vote: the phase is known here)
+        if ((p >> j) & 1) r = ge_add_sel<false, false, 2>(r, &q, true);
     }
     tab[i] = r;
 }

@@ -396,8 +396,8 @@ __global__ __launch_bounds__(TPB) void k_prove_tx(ProveIn in, ProveWs ws, const 
 // ---------------------------------------------------------------- IPA round r
 // item k of proof p (4n'+2 items): a_L_j G[n'+j] | b_R_j H[j] | a_R_j G[j] | b_L_j H[n'+j] (host-normalized
 // MSM terms, vectors.cu:397-398, :430-431) | c_L Q | c_R Q (raw, :402-404, :435-437).  G, H are the
-// ORIGINAL generators every round (the prover never folds them).
-__global__ __launch_bounds__(TPB, 3) void k_prove_rterms(ProveIn in, ProveWs ws, int np, const ge* __restrict__ G,
+// ORIGINAL generators every round (the prover never folds them).  Bounded to 4 waves per SIMD as k_ipa_terms.
+__global__ __launch_bounds__(TPB, 4) void k_prove_rterms(ProveIn in, ProveWs ws, int np, const ge* __restrict__ G,
                                                       const ge* __restrict__ H, const ge* __restrict__ Q,
                                                       const ge* __restrict__ dtab) {
     __shared__ geq qs[TPB];

@@ -150,6 +150,22 @@ template <class M> BP_DEV fe m_sub(const fe& f, const fe& g, M& m) { return fe_s
 template <class M> BP_DEV fe m_mul(const fe& f, const fe& g, M& m) { return fe_mul<M::LAT>(f, g, m.edge(), m.gate()); }
 template <class M> BP_DEV fe m_sq(const fe& f, M& m) { return fe_sq<M::LAT>(f, m.edge(), m.gate()); }
 template <class M> BP_DEV fe m_mul_k(const fe& f, M& m) { return fe_mul_k<M::LAT>(f, m.edge()); }
+#ifndef BP_LANE_GATE_SEEN
+#define BP_LANE_GATE_SEEN 1   // 0: every product of ge_tail puts its own gate words into the running word (A/B builds)
+#endif
+// A product whose two gate words an earlier product of the same form has already put into the Defer
+// mode's running word (a max is idempotent): it runs on a copy of the mode whose gate word is dropped,
+// and with it the statement; the edge word is carried on.  The Gated mode tests in place as everywhere.
+template <class M> BP_DEV fe mul_gate_seen(const fe& f, const fe& g, M& m) {
+    if constexpr (M::LAT == 3 && BP_LANE_GATE_SEEN) {
+        M seen = m;
+        const fe r = m_mul(f, g, seen);
+        m.acc = seen.acc;
+        return r;
+    } else {
+        return m_mul(f, g, m);
+    }
+}
 #ifndef BP_LANE_ADDSUB
 #define BP_LANE_ADDSUB 1
 #endif
@@ -164,6 +180,20 @@ template <class M> BP_DEV void m_addsub(const fe& f, const fe& g, fe& sum, fe& d
 #endif
 }
 
+#ifndef BP_LANE_ADDSUB_ST1
+#define BP_LANE_ADDSUB_ST1 1
+#endif
+// Y1 - X1 and Y1 + X1 of every stage 1: the fused block again (one running word and one chain's wait
+// states fewer per step), or the two calls (-DBP_LANE_ADDSUB_ST1=0, for A/B builds); the same bits.
+template <class M> BP_DEV void ymx_ypx(const ge& p, fe& ymx, fe& ypx, M& m) {
+#if BP_LANE_ADDSUB_ST1
+    m_addsub(p.Y, p.X, ypx, ymx, m);
+#else
+    ymx = m_sub(p.Y, p.X, m);
+    ypx = m_add(p.Y, p.X, m);
+#endif
+}
+
 // ---- ge25519_add (curve25519_ops.cu:326-378 == device_curve25519_ops.cuh:188-241) ----
 // Stage 1 is A = (Y1-X1)(Y2-X2), B = (Y1+X1)(Y2+X2), C = (T1 T2) k and ZZ = Z1 Z2, in that order; the
 // three shapes below differ only there.  ge_tail is stages 2 and 3, the same for all of them.
@@ -173,66 +203,101 @@ BP_DEV ge ge_tail(const fe& A, const fe& B, const fe& C, const fe& ZZ, M& m) {
     fe E, F, G, H;
     m_addsub(B, A, H, E, m);   // H = B + A, E = B - A
     m_addsub(D, C, G, F, m);   // G = D + C, F = D - C
+    // A product's gate reads its first factor's word 0 and its second factor's word 7, and its 512 bits do
+    // not depend on which factor is named first: with Z3 formed as G F the four gates read E0, F7, G0, H7
+    // only, and the first two products have put all four into the running word already.
+#if BP_LANE_GATE_SEEN
+    return ge{m_mul(E, F, m), m_mul(G, H, m), mul_gate_seen(G, F, m), mul_gate_seen(E, H, m)};
+#else
     return ge{m_mul(E, F, m), m_mul(G, H, m), m_mul(F, G, m), m_mul(E, H, m)};
+#endif
 }
 
+// The three shapes are each their stage 1 and the one tail.  TAIL = false stops after stage 1 and hands
+// back (A, B, C, ZZ) in the four slots of a ge, for the per-lane step's vote (ge_add_sel).
+
 // add(p, p) (curve25519_ops.cu:406 / device .cuh:282): the same exact products as squares.
-template <class M>
+template <bool TAIL = true, class M>
 BP_DEV ge ge_dbl(const ge& p, M& m) {
-    fe A = m_sq(m_sub(p.Y, p.X, m), m);
-    fe B = m_sq(m_add(p.Y, p.X, m), m);
+    fe ymx, ypx;
+    ymx_ypx(p, ymx, ypx, m);
+    fe A = m_sq(ymx, m);
+    fe B = m_sq(ypx, m);
     fe C = m_mul_k(m_sq(p.T, m), m);
     fe ZZ = m_sq(p.Z, m);
+    if (!TAIL) return ge{A, B, C, ZZ};
     return ge_tail(A, B, C, ZZ, m);
 }
 
 // add(p, q) with q's prepared operands.
 // zone (wave-uniform): every lane's q.Z is exactly 1 (generators, host-normalized points), so
 // Z1*Z2 = fold(Z1 || 0) = the conditional lossy "- p" of Z1 (fe_mul_one) — same bits, no product.
-template <bool QLDS, class M>
+template <bool QLDS, bool TAIL = true, class M>
 BP_DEV ge ge_add_qp(const ge& p, const geq* q, bool zone, M& m) {
-    fe A = m_mul(m_sub(p.Y, p.X, m), qget<QLDS>(&q->YmX), m);
-    fe B = m_mul(m_add(p.Y, p.X, m), qget<QLDS>(&q->YpX), m);
+    fe ymx, ypx;
+    ymx_ypx(p, ymx, ypx, m);
+    fe A = m_mul(ymx, qget<QLDS>(&q->YmX), m);
+    fe B = m_mul(ypx, qget<QLDS>(&q->YpX), m);
     fe C = m_mul_k(m_mul(p.T, qget<QLDS>(&q->T), m), m);
     fe ZZ = zone ? fe_mul_one(p.Z) : m_mul(p.Z, qget<QLDS>(&q->Z), m);
+    if (!TAIL) return ge{A, B, C, ZZ};
     return ge_tail(A, B, C, ZZ, m);
 }
 
-// One step of the per-lane loop: add(r, r) when !use_q, add(r, q) when use_q; the
-// select is per lane, the operation order is ge25519_add's in both cases.
+#ifndef BP_LANE_VOTE
+#define BP_LANE_VOTE 1   // 0: the per-lane loop's step runs its selected stage 1 on every step (A/B builds)
+#endif
+// One step of the per-lane loop: add(r, r) when !use_q, add(r, q) when use_q, with a wave vote on its
+// stage 1.  Lanes with the same scalar are in the same phase at every step, and after the verify's lane
+// sort a fold round's wave holds few distinct scalars: when every lane still in the loop doubles, the step
+// runs the doubling's stage 1 (squares, no selects), when every one adds, the add's (q's operands straight
+// from the slot, no Z^2); else its own, where the select is per lane.  One ballot over the active lanes (a
+// lane that has left the loop is not in exec and has no say), one scalar branch, one copy of the tail; the
+// operation order is ge25519_add's in every body and each forms the same exact products, so the bits are
+// the same whichever runs.  PATH forces a body (the instruction-count probes, BP_LANE_VOTE 0): 0 doubling,
+// 1 add, 2 selected; -1 votes.
 // ZONE (wave-uniform): every lane's q.Z is exactly 1, so the add lanes' Z1*Z2 is fe_mul_one(Z1)
 // and the doubling lanes' is the square Z1^2 — both formed, one kept (the same bits as the
 // general product; 150 + ~20 VALU instead of 189 + the operand select).
-template <bool QLDS, bool ZONE = false, class M>
+template <bool QLDS, bool ZONE = false, int PATH = (BP_LANE_VOTE ? -1 : 2), class M>
 BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q, M& m) {
-    // q's operands are loaded unconditionally and selected as values: a select between a
-    // loaded and a computed value is otherwise folded into a load through a select of
-    // pointers, which forces `p` into private memory (scratch).
-    fe ymx = m_sub(p.Y, p.X, m);
-    fe qa = qget<QLDS>(&q->YmX);
-    fe A = m_mul(ymx, use_q ? qa : ymx, m);
-    fe ypx = m_add(p.Y, p.X, m);
-    fe qb = qget<QLDS>(&q->YpX);
-    fe B = m_mul(ypx, use_q ? qb : ypx, m);
-    fe qt = qget<QLDS>(&q->T);
-    fe C = m_mul_k(m_mul(p.T, use_q ? qt : p.T, m), m);
-    fe ZZ;
-    if (ZONE) {
-        fe d1 = fe_mul_one(p.Z), d2 = m_sq(p.Z, m);
-        ZZ = use_q ? d1 : d2;
+    const uint64_t adds = __builtin_amdgcn_ballot_w64(use_q), live = __builtin_amdgcn_ballot_w64(true);
+    ge s;   // stage 1: A, B, C, ZZ
+    if (PATH == 0 || (PATH < 0 && adds == 0)) {
+        s = ge_dbl<false>(p, m);
+    } else if (PATH == 1 || (PATH < 0 && adds == live)) {
+        s = ge_add_qp<QLDS, false>(p, q, ZONE, m);
     } else {
-        fe qz = qget<QLDS>(&q->Z);
-        ZZ = m_mul(p.Z, use_q ? qz : p.Z, m);
+        // q's operands are loaded unconditionally and selected as values: a select between a
+        // loaded and a computed value is otherwise folded into a load through a select of
+        // pointers, which forces `p` into private memory (scratch).
+        fe ymx, ypx;
+        ymx_ypx(p, ymx, ypx, m);
+        fe qa = qget<QLDS>(&q->YmX);
+        s.X = m_mul(ymx, use_q ? qa : ymx, m);
+        fe qb = qget<QLDS>(&q->YpX);
+        s.Y = m_mul(ypx, use_q ? qb : ypx, m);
+        fe qt = qget<QLDS>(&q->T);
+        s.Z = m_mul_k(m_mul(p.T, use_q ? qt : p.T, m), m);
+        if (ZONE) {
+            // (the square first: with fe_mul_one first, k_terms<1>'s deferred loop reloads a spilled pair
+            // after this body, profiles/NOTES.md §15)
+            fe d2 = m_sq(p.Z, m), d1 = fe_mul_one(p.Z);
+            s.T = use_q ? d1 : d2;
+        } else {
+            fe qz = qget<QLDS>(&q->Z);
+            s.T = m_mul(p.Z, use_q ? qz : p.Z, m);
+        }
     }
-    return ge_tail(A, B, C, ZZ, m);
+    return ge_tail(s.X, s.Y, s.Z, s.T, m);
 }
 
 // The gated mode under the plain names (every caller outside the lane loops' deferred pass).
 BP_DEV ge ge_dbl(const ge& p) { Gated m; return ge_dbl(p, m); }
 template <bool QLDS>
 BP_DEV ge ge_add_qp(const ge& p, const geq* q, bool zone = false) { Gated m; return ge_add_qp<QLDS>(p, q, zone, m); }
-template <bool QLDS, bool ZONE = false>
-BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q) { Gated m; return ge_add_sel<QLDS, ZONE>(p, q, use_q, m); }
+template <bool QLDS, bool ZONE = false, int PATH = (BP_LANE_VOTE ? -1 : 2)>
+BP_DEV ge ge_add_sel(const ge& p, const geq* q, bool use_q) { Gated m; return ge_add_sel<QLDS, ZONE, PATH>(p, q, use_q, m); }
 BP_DEV ge ge_add_q(const ge& p, const geq& q) { return ge_add_qp<false>(p, &q); }
 BP_DEV ge ge_add(const ge& p, const ge& q) { return ge_add_q(p, ge_prep(q)); }
 

@@ -15,7 +15,7 @@ extern "C" __global__ void p_ge_add_q(ge* o, const ge* p, const geq* q) { o[thre
 extern "C" __global__ void p_ge_add_sel(ge* o, const ge* p, const geq* q, const int* u) {
     __shared__ geq qs[256];
     qs[threadIdx.x] = q[threadIdx.x];
-    o[threadIdx.x] = ge_add_sel<true>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0);
+    o[threadIdx.x] = ge_add_sel<true, false, 2>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0);
 }
 extern "C" __global__ void p_fe_sq(fe* o, const fe* a) { o[threadIdx.x] = fe_sq(a[threadIdx.x]); }
 extern "C" __global__ void p_ge_add_zone(ge* o, const ge* p, const geq* q) {
@@ -26,7 +26,7 @@ extern "C" __global__ void p_ge_add_zone(ge* o, const ge* p, const geq* q) {
 extern "C" __global__ void p_ge_add_sel_zone(ge* o, const ge* p, const geq* q, const int* u) {
     __shared__ geq qs[256];
     qs[threadIdx.x] = q[threadIdx.x];
-    o[threadIdx.x] = ge_add_sel<true, true>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0);
+    o[threadIdx.x] = ge_add_sel<true, true, 2>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0);
 }
 // the same forms in the Defer mode (ge25519_dev.h: the lane loops' common pass), the running test words written out
 extern "C" __global__ void p_ge_dbl_d(ge* o, const ge* p, uint32_t* w) {
@@ -45,9 +45,23 @@ extern "C" __global__ void p_ge_add_sel_zone_d(ge* o, const ge* p, const geq* q,
     __shared__ geq qs[256];
     qs[threadIdx.x] = q[threadIdx.x];
     Defer d;
-    o[threadIdx.x] = ge_add_sel<true, true>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0, d);
+    o[threadIdx.x] = ge_add_sel<true, true, 2>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0, d);
     w[threadIdx.x] = d.acc | d.gacc;
 }
+// the per-lane loop's step (ge_add_sel) with its vote forced each way: all lanes doubling, all
+// adding, mixed (the selected stage 1); and with the vote itself (all three bodies, one tail)
+#define VOTE_PROBE(name, path)                                                                                  \
+    extern "C" __global__ void name(ge* o, const ge* p, const geq* q, const int* u, uint32_t* w) {              \
+        __shared__ geq qs[256];                                                                                 \
+        qs[threadIdx.x] = q[threadIdx.x];                                                                       \
+        Defer d;                                                                                                \
+        o[threadIdx.x] = ge_add_sel<true, true, path>(p[threadIdx.x], &qs[threadIdx.x], u[threadIdx.x] != 0, d); \
+        w[threadIdx.x] = d.acc | d.gacc;                                                                        \
+    }
+VOTE_PROBE(p_ge_add_vote_zone_d_dbl, 0)
+VOTE_PROBE(p_ge_add_vote_zone_d_add, 1)
+VOTE_PROBE(p_ge_add_vote_zone_d_sel, 2)
+VOTE_PROBE(p_ge_add_vote_zone_d, -1)
 extern "C" __global__ void p_fe_canon(fe* o, const fe* a) { o[threadIdx.x] = fe_canon(a[threadIdx.x]); }
 // one step of the drain-tick forms (sm_quad / sm_pair loop bodies): the latency-bound chains
 #include "../cudabulletproof_amd/csrc/ge25519_quad.h"
