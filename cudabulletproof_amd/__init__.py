@@ -24,7 +24,7 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libcudabulletproof_hip.so")
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["bp_terms1.hip", "bp_terms2.hip", "bp_terms4.hip", "bp_terms16.hip", "bp_kernels.hip", "bp_prove.hip",
-           "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_commit.hip", "bp_capi.hip"]
+           "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_commit.hip", "bp_codec.hip", "bp_capi.hip"]
 
 _lib = None
 
@@ -99,6 +99,11 @@ class ProofOutC(ctypes.Structure):   # hipbp_proof_out
     _fields_ = [(k, _c) for k in ("V", "A", "S", "T1", "T2", "taux", "mu", "t", "c", "x", "a", "b", "L", "R", "valid")]
 
 
+class ProofBlobInfoC(ctypes.Structure):   # hipbp_proof_blob_info
+    _fields_ = [("count", _sz), ("n", _sz), ("ab_len", _sz), ("L_len", _sz), ("flags", ctypes.c_uint),
+                ("raw_count", _sz), ("bytes", _sz)]
+
+
 class ProveIpaInputC(ctypes.Structure):   # hipbp_ipa_prove_input
     _fields_ = [("count", _sz), ("n", _sz)] + [(k, _c) for k in ("a", "b", "c", "transcript")]
 
@@ -133,6 +138,9 @@ EXPORTS = [
     "hipbp_batch_generate_range_proof_host_sharded", "hipbp_batch_generate_range_proof_accepted_host",
     "hipbp_batch_pedersen_commit", "hipbp_batch_pedersen_commit_gens", "hipbp_batch_pedersen_open",
     "hipbp_batch_pedersen_commit_host",
+    "hipbp_proof_blob_bound", "hipbp_proof_blob_header", "hipbp_proof_blob_parse", "hipbp_batch_proof_encode",
+    "hipbp_batch_proof_decode", "hipbp_proofs_encode_host", "hipbp_proofs_decode_host",
+    "hipbp_batch_range_proof_verify_bytes_host",
 ]
 
 
@@ -167,8 +175,11 @@ def lib():
                   "hipbp_derive_prover_scalars_at", "hipbp_accepted_last_stats",
                   "hipbp_batch_generate_range_proof_host_sharded", "hipbp_batch_generate_range_proof_accepted_host",
                   "hipbp_batch_pedersen_commit", "hipbp_batch_pedersen_commit_gens", "hipbp_batch_pedersen_open",
-                  "hipbp_batch_pedersen_commit_host"):
+                  "hipbp_batch_pedersen_commit_host", "hipbp_proof_blob_header", "hipbp_proof_blob_parse",
+                  "hipbp_batch_proof_encode", "hipbp_batch_proof_decode", "hipbp_proofs_encode_host",
+                  "hipbp_proofs_decode_host", "hipbp_batch_range_proof_verify_bytes_host"):
             getattr(L, f).restype = ctypes.c_int
+        L.hipbp_proof_blob_bound.restype = ctypes.c_size_t
         _lib = L
     return _lib
 
@@ -793,6 +804,142 @@ def batch_pedersen_commit_host(v, gamma, g, h, num_gpus=1):
     return out
 
 
+# ---------------------------------------------------------------------- compact proof blobs
+def _blob_info(ic):
+    return dict(count=int(ic.count), n=int(ic.n), ab_len=int(ic.ab_len), L_len=int(ic.L_len), flags=int(ic.flags),
+                raw_count=int(ic.raw_count), bytes=int(ic.bytes))
+
+
+def _blob_arg(blob):
+    """A host blob (bytes, bytearray, memoryview or a uint8 array) as a contiguous uint8 array."""
+    if isinstance(blob, np.ndarray):
+        return np.ascontiguousarray(blob, np.uint8).reshape(-1)
+    return np.frombuffer(bytes(blob), np.uint8)
+
+
+def proof_blob_info(blob):
+    """hipbp_proof_blob_parse: fully validates a host proof blob ("HBPC" version 1) and
+    returns dict(count, n, ab_len, L_len, flags (bit 0: taux and mu stored), raw_count, bytes).
+    Raises BulletproofError with the reason on a malformed blob.  CPU only: needs no GPU."""
+    b = _blob_arg(blob)
+    ic = ProofBlobInfoC()
+    _chk(lib().hipbp_proof_blob_parse(_p(b), _sz(len(b)), ctypes.byref(ic)))
+    return _blob_info(ic)
+
+
+def proofs_to_bytes(proofs, n, with_blinding=False):
+    """hipbp_proofs_encode_host: a list of proof dicts (what cuda_range_proof_verify and
+    batch_range_proof_verify_host take: head (100,) = V,A,S,T1,T2 | taux,mu,t,c,x; a, b (k,4); L, R
+    (m,16)) as one compact blob, returned as bytes.  A proof whose points are normalized (Z = 1, T = X Y)
+    and whose a = [t], b = [1], c = t, limb for limb, takes 64 bytes per point; any other is stored
+    verbatim, so proofs_from_bytes returns every limb.  with_blinding: taux and mu are stored.  The
+    first proof sets the shape; a proof of another shape raises.  CPU only: needs no GPU; the bytes
+    are encode_proofs'."""
+    keep = []
+    count = len(proofs)
+    arr = (RangeProofC * max(count, 1))()
+    for i, pr in enumerate(proofs):
+        arr[i] = _range_proof_struct(pr, n, keep)
+    abl = len(keep[0]) if count else 1
+    Lr = len(keep[2]) if count else 0
+    cap = lib().hipbp_proof_blob_bound(_sz(count), _sz(abl), _sz(Lr), ctypes.c_uint(1 if with_blinding else 0))
+    out = np.zeros(cap, np.uint8)
+    nb = _sz(0)
+    _chk(lib().hipbp_proofs_encode_host(arr, _sz(count), _sz(int(n)), ctypes.c_int(1 if with_blinding else 0), _p(out),
+                                        _sz(cap), ctypes.byref(nb)))
+    return out[:nb.value].tobytes()
+
+
+def proofs_from_bytes(blob):
+    """hipbp_proofs_decode_host: the proofs of a host blob as a list of proof dicts (head, a, b, L, R,
+    n, L_len; taux and mu zero when the blob does not store them), bit for bit what was encoded.
+    Raises BulletproofError on a malformed blob.  CPU only: needs no GPU."""
+    b = _blob_arg(blob)
+    count = proof_blob_info(b)["count"]
+    arr = (RangeProofC * max(count, 1))()
+    _chk(lib().hipbp_proofs_decode_host(_p(b), _sz(len(b)), arr))
+    return _take_proofs(arr, count)
+
+
+def encode_proofs(batch, with_blinding=False, stream=None):
+    """hipbp_batch_proof_encode: a RangeProofBatch as one compact blob on its device (classify, scan
+    and write launches; the bytes are proofs_to_bytes').  with_blinding needs batch.taux / batch.mu.
+    The V encoded is batch.Vp when present, else batch.V.  Returns a uint8 CUDA tensor trimmed to the
+    written size (the call waits for the stream to read that size)."""
+    import contextlib
+
+    import torch
+    f = 1 if with_blinding else 0
+    cap = lib().hipbp_proof_blob_bound(_sz(batch.count), _sz(batch.ab_len), _sz(batch.L_len), ctypes.c_uint(f))
+    dev = batch.V.device
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        blob = torch.empty(cap, dtype=torch.uint8, device=dev)
+        nb = torch.zeros(1, dtype=torch.int64, device=dev)
+    s = batch.c_struct()
+    _chk(lib().hipbp_batch_proof_encode(ctypes.byref(s), ctypes.c_int(f), _c(blob.data_ptr()), _sz(cap),
+                                        _c(nb.data_ptr()), _stream_ptr(stream)))
+    _chk(lib().hipbp_sync(_stream_ptr(stream)))
+    return blob[:int(nb.item())]
+
+
+def decode_proofs(blob_tensor, stream=None):
+    """hipbp_batch_proof_decode: a blob in a uint8 CUDA tensor as a RangeProofBatch on its device
+    (taux / mu present when the blob stores them).  The 32 header bytes are read back and validated
+    on the host (hipbp_proof_blob_header); the kernels check every index they take from the blob
+    and skip what fails: a non-zero count of skipped records raises.  Waits for the stream."""
+    import contextlib
+
+    import torch
+    blob_tensor = blob_tensor.contiguous()
+    if blob_tensor.dtype != torch.uint8 or blob_tensor.dim() != 1:
+        raise ValueError("blob_tensor must be a 1-D uint8 tensor")
+    head = blob_tensor[:32].cpu().numpy()
+    if len(head) < 32:
+        raise BulletproofError("proof_blob_header: blob shorter than its header")
+    ic = ProofBlobInfoC()
+    _chk(lib().hipbp_proof_blob_header(_p(head), _sz(blob_tensor.numel()), ctypes.byref(ic)))
+    B, n, abl, Lr, f = int(ic.count), int(ic.n), int(ic.ab_len), int(ic.L_len), int(ic.flags) & 1
+    dev = blob_tensor.device
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+        out = dict(V=z(B, 16), A=z(B, 16), S=z(B, 16), T1=z(B, 16), T2=z(B, 16), taux=z(B, 4) if f else None,
+                   mu=z(B, 4) if f else None, t=z(B, 4), c=z(B, 4), x=z(B, 4), a=z(B, abl, 4), b=z(B, abl, 4),
+                   L=z(B, Lr, 16), R=z(B, Lr, 16), valid=None)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    oc = ProofOutC(*[out[k].data_ptr() if out[k] is not None and out[k].numel() else None for k in _PROOF_KEYS])
+    _chk(lib().hipbp_batch_proof_decode(_c(blob_tensor.data_ptr()), ctypes.byref(ic), ctypes.byref(oc),
+                                        _c(bad.data_ptr()), _stream_ptr(stream)))
+    _chk(lib().hipbp_sync(_stream_ptr(stream)))
+    if int(bad.item()):
+        raise BulletproofError(f"decode_proofs: {int(bad.item())} record(s) failed their checks and were skipped")
+    del out["valid"]
+    return RangeProofBatch(n, **out)
+
+
+def batch_range_proof_verify_bytes_host(blob, n, G, H, g, h, V=None, check=1, num_gpus=1):
+    """hipbp_batch_range_proof_verify_bytes_host: verifies the proofs of a host blob on the GPU(s),
+    uploading the blob's bytes (about half the structs').  check 1: cuda_range_proof_verify
+    semantics, the verdicts of batch_range_proof_verify_host on proofs_from_bytes(blob); check 2:
+    range_proof_verify semantics (batch_range_proof_verify_std's verdicts; the blob must store taux
+    and mu).  V (count,16): the verify's V argument; None: each proof's own V.  G, H (n,16), g, h
+    (16,) uint64.  num_gpus as in batch_range_proof_verify_host.  Returns (count,) bool."""
+    require_gpu()
+    b = _blob_arg(blob)
+    count = proof_blob_info(b)["count"]
+    g, h = _u64(g, 16), _u64(h, 16)
+    G, H = _u64(G, 16), _u64(H, 16)
+    if V is not None:
+        V = _u64(V, 16).reshape(-1, 16)
+        if len(V) != count:
+            raise ValueError(f"V must be ({count}, 16)")
+    gv, hv = PointVector(_p(G).value, len(G)), PointVector(_p(H).value, len(H))
+    ok = np.zeros(max(count, 1), np.uint8)
+    _chk(lib().hipbp_batch_range_proof_verify_bytes_host(_p(b), _sz(len(b)), _p(V) if V is not None else None,
+                                                         _sz(int(n)), ctypes.byref(gv), ctypes.byref(hv), _p(g), _p(h),
+                                                         ctypes.c_int(check), ctypes.c_int(num_gpus), _p(ok)))
+    return ok[:count].astype(bool)
+
+
 def batch_inner_product_prove(n, a, b, c, G, H, Q, transcript=None, stream=None, gens=None):
     """inner_product_prove (bulletproof_vectors.cu:277) over a batch, on the GPU, for any power-of-two
     n up to 65536 (hipbp_batch_inner_product_prove).
@@ -936,7 +1083,7 @@ def msm_pippenger_horner(results, window_sums, window_bits=12, stream=None):
 
 def release_stream_workspaces(stream=None):
     """hipbp_release_stream_workspaces: free every workspace cached for `stream` on the current
-    device (MSM, prover, commitments, one-shot pipelines, Pippenger pair); call before dropping a stream."""
+    device (MSM, prover, commitments, blob encoder, one-shot pipelines, Pippenger pair); call before dropping a stream."""
     _chk(lib().hipbp_release_stream_workspaces(_stream_ptr(stream)))
 
 

@@ -24,6 +24,7 @@
 #include "bp_host_prove.h"
 #include "ge25519_dev.h"
 #include "bp_prove_seed.h"
+#include "bp_codec.h"
 
 static_assert(sizeof(fe25519) == 32, "fe25519 layout");
 static_assert(sizeof(ge25519) == 128, "ge25519 layout");
@@ -131,6 +132,7 @@ struct StreamWs {
     hipEvent_t ipa_ev[2] = {};   // [0] the caller's stream at entry, [1] the side stream's last chunk done
     bp::PipPair pip;             // Pippenger MSM (hipbp_msm_pippenger*): both parts' buffers and its side stream
     Buf commit[bp::CB_COUNT];    // Pedersen commitments (hipbp_batch_pedersen_commit*): one chunk's terms
+    Buf codec[bp::CDB_COUNT];    // proof blob encoder (hipbp_batch_proof_encode): the block counts
     std::map<std::pair<int, int>, Pipeline*> pipes;   // one-shot verify pipelines, per (n, mode)
     hipError_t release(hipError_t first);
 };
@@ -572,6 +574,7 @@ hipError_t StreamWs::release(hipError_t first) {
     for (auto& b : accept) keep(b.release());
     keep(accept_cnt.release());
     for (auto& b : commit) keep(b.release());
+    for (auto& b : codec) keep(b.release());
     if (ipa_side) keep(hipStreamSynchronize(ipa_side));
     for (auto& half : ipa)
         for (auto& b : half) keep(b.release());
@@ -2253,45 +2256,164 @@ bool cuda_inner_product_verify(const InnerProductProof* proof, const ge25519* P,
 
 namespace {
 
-// one device's shard of hipbp_batch_range_proof_verify_host (its own host thread).  The shard is cut
-// into chunks of CHUNK proofs, each staged as its own little flat batch; each chunk is packed,
-// copied and pushed as soon as it is packed (the GPU starts while the host packs the rest), and
+// What a shard of the host verifiers takes its 1024-proof chunks from.  host_bytes / dev_bytes: the
+// chunk's pinned and device staging; stage: fills the pinned bytes at hc, enqueues on s what leaves the
+// flat chunk at dc, and views it as *b (`word`: a zeroed device word of the shard's, summed into by a
+// source that counts something); out_index: where proof k of the shard's verdicts goes.
+//
+// The caller's host structs (hipbp_batch_range_proof_verify_host): packed on the host, copied as they are.
+struct StructChunks {
+    const RangeProof* proofs;
+    const ge25519* V;
+    const size_t* idx;
+    size_t abl, Lr, n;
+    size_t host_bytes(size_t, size_t c) const { return bp::ChunkLayout{c, abl, Lr}.bytes(); }
+    size_t dev_bytes(size_t c0, size_t c) const { return host_bytes(c0, c); }
+    size_t out_index(size_t k) const { return idx[k]; }
+    int stage(size_t c0, size_t c, uint8_t* hc, uint8_t* dc, uint32_t*, hipStream_t s, hipbp_proof_batch* b) const {
+        const bp::ChunkLayout lay{c, abl, Lr};
+        for (size_t k = 0; k < c; k++) {
+            const RangeProof& p = proofs[idx[c0 + k]];
+            lay.pack(hc, k, p.ip_proof, &p, &V[idx[c0 + k]]);
+        }
+        hipError_t err = hipMemcpyAsync(dc, hc, lay.bytes(), hipMemcpyHostToDevice, s);
+        if (err != hipSuccess) {
+            g_err = std::string("chunk H2D: ") + hipGetErrorString(err);
+            return HIPBP_ERR_DEVICE;
+        }
+        memset(b, 0, sizeof *b);
+        b->n = n;
+        lay.view(dc, b);
+        return HIPBP_OK;
+    }
+};
+
+inline size_t pad16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// A host blob's proofs [lo, lo + B) (hipbp_batch_range_proof_verify_bytes_host; the blob parsed by the
+// caller): a chunk uploads its kind bytes, its compact slots, its raw_index entries and raw records
+// (raw_index is ascending: two binary searches bound them) and the caller's V rows, each part at a
+// 16-byte boundary, and decodes them on the chunk's stream into a flat chunk behind the copy, with
+// taux | mu after it when the blob has them.
+struct BlobChunks {
+    const uint8_t* blob;
+    bp::CodecLayout l;   // the whole blob's
+    size_t R, n, lo;
+    const ge25519* V;    // the caller's, or null: each proof's own
+    struct Parts { size_t j0, nr, o_cmp, o_idx, o_raw, o_v, slice, o_flat, o_tm, end; };
+    Parts parts(size_t c0, size_t c) const {
+        Parts p;
+        const uint8_t* ri = blob + l.o_rawidx();
+        p.j0 = bp::codec_raw_lower(ri, R, lo + c0);
+        p.nr = bp::codec_raw_lower(ri, R, lo + c0 + c) - p.j0;
+        p.o_cmp = pad16(c);
+        p.o_idx = p.o_cmp + c * l.Sc();
+        p.o_raw = p.o_idx + pad16(4 * p.nr);
+        p.o_v = p.o_raw + pad16(p.nr * l.Sr());
+        p.slice = p.o_v + (V ? c * bp::GE : 0);
+        p.o_flat = (p.slice + 127) & ~(size_t)127;
+        p.o_tm = p.o_flat + bp::ChunkLayout{c, l.abl, l.Lr}.bytes();
+        p.end = p.o_tm + (l.f ? 2 * c * bp::FE : 0);
+        return p;
+    }
+    size_t host_bytes(size_t c0, size_t c) const { return (parts(c0, c).slice + 127) & ~(size_t)127; }
+    size_t dev_bytes(size_t c0, size_t c) const { return (parts(c0, c).end + 127) & ~(size_t)127; }
+    size_t out_index(size_t k) const { return lo + k; }
+    int stage(size_t c0, size_t c, uint8_t* hc, uint8_t* dc, uint32_t* word, hipStream_t s, hipbp_proof_batch* b) const {
+        const Parts p = parts(c0, c);
+        const size_t P0 = lo + c0;
+        memcpy(hc, blob + l.o_kind() + P0, c);
+        memcpy(hc + p.o_cmp, blob + l.o_compact() + P0 * l.Sc(), c * l.Sc());
+        memcpy(hc + p.o_idx, blob + l.o_rawidx() + 4 * p.j0, 4 * p.nr);
+        memcpy(hc + p.o_raw, blob + l.o_raw(R) + p.j0 * l.Sr(), p.nr * l.Sr());
+        if (V) memcpy(hc + p.o_v, V + P0, c * bp::GE);
+        hipError_t err = hipMemcpyAsync(dc, hc, p.slice, hipMemcpyHostToDevice, s);
+        if (err != hipSuccess) {
+            g_err = std::string("chunk H2D: ") + hipGetErrorString(err);
+            return HIPBP_ERR_DEVICE;
+        }
+        memset(b, 0, sizeof *b);
+        b->n = n;
+        bp::ChunkLayout{c, l.abl, l.Lr}.view(dc + p.o_flat, b);
+        bp::CodecArrays A;
+        const ge25519* pts[5] = {b->V, b->A, b->S, b->T1, b->T2};
+        for (int k = 0; k < 5; k++) A.pt[k] = (bp::ge*)pts[k];
+        A.t = (bp::fe*)b->t; A.c = (bp::fe*)b->c; A.x = (bp::fe*)b->x; A.a = (bp::fe*)b->a; A.b = (bp::fe*)b->b;
+        A.L = (bp::ge*)b->L; A.R = (bp::ge*)b->R;
+        A.taux = l.f ? (bp::fe*)(dc + p.o_tm) : nullptr;
+        A.mu = l.f ? A.taux + c : nullptr;
+        b->taux = (const fe25519*)A.taux; b->mu = (const fe25519*)A.mu;
+        if (V) {   // the verify's V argument is the caller's; the proof's own V stays where it was decoded
+            b->Vp = b->V;
+            b->V = (const ge25519*)(dc + p.o_v);
+        }
+        bp::BlobView v;
+        v.kind = dc; v.compact = dc + p.o_cmp; v.rawidx = dc + p.o_idx; v.raw = dc + p.o_raw;
+        v.count = c; v.R = p.nr; v.base = P0;
+        v.kind_n = v.compact_n = c; v.rawidx_n = v.raw_n = p.nr;
+        bp::launch_codec_decode(v, A, l, word, s);
+        if ((err = hipGetLastError()) != hipSuccess) {
+            g_err = std::string("chunk decode: ") + hipGetErrorString(err);
+            return HIPBP_ERR_DEVICE;
+        }
+        return HIPBP_OK;
+    }
+};
+
+// one device's shard of a host verifier (its own host thread): B proofs from `src`.  The shard is cut
+// into chunks of CHUNK proofs, each staged as its own little flat batch; each chunk is staged,
+// copied and pushed as soon as it is staged (the GPU starts while the host stages the rest), and
 // the chunks alternate over two pipelines on two streams, whose ticks fill each other's tails.
-int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t* idx, size_t B, size_t abl,
-               size_t Lr, size_t n, const PointVector* G, const PointVector* H, const ge25519* h, uint8_t* ok) {
+// mode 1: cuda_range_proof_verify semantics, with the cached host prefix tables; mode 2:
+// range_proof_verify semantics (g read), without tables.
+template <class Src>
+int host_shard(int dev, const Src& src, size_t B, size_t n, const PointVector* G, const PointVector* H,
+               const ge25519* g, const ge25519* h, int mode, uint8_t* ok) {
     BP_RET_ON(hipSetDevice(dev));
     BP_ENGINE_OR_RET(e);
     constexpr size_t CHUNK = 1024;
     const size_t GE = bp::GE;
-    auto chunk_bytes = [&](size_t c) { return bp::ChunkLayout{c, abl, Lr}.bytes(); };
     const size_t nch = (B + CHUNK - 1) / CHUNK;
-    const size_t gen_off = chunk_bytes(CHUNK) * (nch - 1) + chunk_bytes(B - CHUNK * (nch - 1));
-    const size_t ok_off = gen_off + (2 * n + 1) * GE, bytes = ok_off + B;
+    size_t hsum = 0, dsum = 0;
+    for (size_t ch = 0; ch < nch; ch++) {
+        const size_t c0 = ch * CHUNK, c = std::min(CHUNK, B - c0);
+        hsum += src.host_bytes(c0, c);
+        dsum += src.dev_bytes(c0, c);
+    }
+    // after the chunks: G | H | h | g, the verdicts, and the source's counter word
+    const size_t tail = (2 * n + 2) * GE + pad16(B) + 16;
+    const size_t gen_off_h = hsum, gen_off = dsum, ok_off_h = gen_off_h + (2 * n + 2) * GE, ok_off = gen_off + (2 * n + 2) * GE;
+    const size_t bytes_h = hsum + tail, bytes = dsum + tail;
     std::lock_guard<std::mutex> lk(e->mu);
     if (!e->stream2) BP_RET_ON(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
     hipStream_t st[2] = {e->stream, e->stream2};
     // need() frees a buffer that grows: nothing may still read either
-    if ((bytes > e->host_pinned.cap && e->host_pinned.p) || bytes > e->host_dev.cap) {
+    if ((bytes_h > e->host_pinned.cap && e->host_pinned.p) || bytes > e->host_dev.cap) {
         BP_RET_ON(hipStreamSynchronize(st[0]));
         BP_RET_ON(hipStreamSynchronize(st[1]));
     }
-    BP_RET_ON(e->host_pinned.need(bytes));
+    BP_RET_ON(e->host_pinned.need(bytes_h));
     BP_RET_ON(e->host_dev.need(bytes));
     uint8_t* host = e->host_pinned.as<uint8_t>();
     uint8_t* dbuf = e->host_dev.as<uint8_t>();
-    memcpy(host + gen_off, G->elements, n * GE);
-    memcpy(host + gen_off + n * GE, H->elements, n * GE);
-    memcpy(host + gen_off + 2 * n * GE, h, GE);
-    BP_RET_ON(hipMemcpyAsync(dbuf + gen_off, host + gen_off, (2 * n + 1) * GE, hipMemcpyHostToDevice, st[0]));
+    memcpy(host + gen_off_h, G->elements, n * GE);
+    memcpy(host + gen_off_h + n * GE, H->elements, n * GE);
+    memcpy(host + gen_off_h + 2 * n * GE, h, GE);
+    if (mode == 2) memcpy(host + gen_off_h + (2 * n + 1) * GE, g, GE);
+    BP_RET_ON(hipMemcpyAsync(dbuf + gen_off, host + gen_off_h, (2 * n + (mode == 2 ? 2 : 1)) * GE, hipMemcpyHostToDevice,
+                             st[0]));
+    uint32_t* word = (uint32_t*)(dbuf + ok_off + pad16(B));
+    BP_RET_ON(hipMemsetAsync(word, 0, 16, st[0]));
     BP_RET_ON(e->ensure_two((int)n));   // engine stream: ordered before the pipeline's first tick
     const ge25519* dgen = (const ge25519*)(dbuf + gen_off);
     // the generators' prefix tables: reused when this call's generator bytes equal the cached set's
     // (then the pipelines read this call's copy and the tables built from identical bytes)
     int hb = 16;
     if (const char* pb = getenv("HIPBP_HOST_PREFIX_BITS")) hb = std::max(0, std::min(atoi(pb), bp::PREFIX_MAX_BITS));
+    if (mode == 2) hb = 0;
     while (hb > 0 && ((2 * n + 2) << hb) * GE > (size_t(5) << 28)) hb--;   // at most 1.25 GB of tables (K = 12 at n = 1024)
     if (hb > 0) {
-        const uint8_t* key = host + gen_off;
+        const uint8_t* key = host + gen_off_h;
         const size_t kb = (2 * n + 1) * GE;
         if (e->host_tab_bits != hb || e->host_gens_key.size() != kb || memcmp(e->host_gens_key.data(), key, kb) != 0) {
             e->host_tab_bits = 0;
@@ -2318,9 +2440,9 @@ int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t
     Pipeline* pl[2] = {nullptr, nullptr};
     int rc = HIPBP_OK;
     for (int k = 0; k < 2 && rc == HIPBP_OK; k++) {
-        rc = pipeline_for(*e, st[k], std::min(B, CHUNK), (int)n, 1, &pl[k]);
+        rc = pipeline_for(*e, st[k], std::min(B, CHUNK), (int)n, mode, &pl[k]);
         if (rc == HIPBP_OK) {
-            pl[k]->set_gens(dgen, dgen + n, nullptr, dgen + 2 * n);
+            pl[k]->set_gens(dgen, dgen + n, mode == 2 ? dgen + 2 * n + 1 : nullptr, dgen + 2 * n);
             // (the engine's one-shot pipelines are shared with the other entry points: the tables
             // are lent for this call only and taken back after the flush below)
             pl[k]->ext_tab = hb > 0 ? e->host_tab.as<bp::ge>() : nullptr;
@@ -2328,34 +2450,20 @@ int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t
         }
     }
     hipEvent_t gens_ready = nullptr;
-    if (rc == HIPBP_OK) {   // the second stream waits for the generators' copy
+    if (rc == HIPBP_OK) {   // the second stream waits for the generators' copy (and the zeroed word)
         BP_RET_ON(hipEventCreateWithFlags(&gens_ready, hipEventDisableTiming));
         BP_RET_ON(hipEventRecord(gens_ready, st[0]));
         BP_RET_ON(hipStreamWaitEvent(st[1], gens_ready, 0));
     }
     uint8_t* dok = dbuf + ok_off;
-    size_t off = 0;
+    size_t off_h = 0, off = 0;
     for (size_t ch = 0; ch < nch && rc == HIPBP_OK; ch++) {
         const size_t c0 = ch * CHUNK, c = std::min(CHUNK, B - c0);
-        const bp::ChunkLayout lay{c, abl, Lr};
-        const size_t cb = lay.bytes();
-        uint8_t* hc = host + off;
-        for (size_t k = 0; k < c; k++) {
-            const RangeProof& p = proofs[idx[c0 + k]];
-            lay.pack(hc, k, p.ip_proof, &p, &V[idx[c0 + k]]);
-        }
-        hipStream_t s = st[ch & 1];
-        if ((err = hipMemcpyAsync(dbuf + off, hc, cb, hipMemcpyHostToDevice, s)) != hipSuccess) {
-            g_err = std::string("chunk H2D: ") + hipGetErrorString(err);
-            rc = HIPBP_ERR_DEVICE;
-            break;
-        }
         hipbp_proof_batch b;
-        memset(&b, 0, sizeof b);
-        b.n = n;
-        lay.view(dbuf + off, &b);
+        if ((rc = src.stage(c0, c, host + off_h, dbuf + off, word, st[ch & 1], &b)) != HIPBP_OK) break;
         rc = pl[ch & 1]->push(&b, nullptr, dok + c0, nullptr, nullptr);
-        off += cb;
+        off_h += src.host_bytes(c0, c);
+        off += src.dev_bytes(c0, c);
     }
     for (int k = 0; k < 2 && rc == HIPBP_OK; k++) rc = pl[k]->flush();
     for (int k = 0; k < 2; k++)
@@ -2365,17 +2473,79 @@ int host_shard(int dev, const RangeProof* proofs, const ge25519* V, const size_t
         }
     hipError_t s1 = hipStreamSynchronize(st[1]);
     if (rc == HIPBP_OK && s1 == hipSuccess) {
-        if ((err = hipMemcpyAsync(host + ok_off, dok, B, hipMemcpyDeviceToHost, st[0])) == hipSuccess)
+        if ((err = hipMemcpyAsync(host + ok_off_h, dok, pad16(B) + 16, hipMemcpyDeviceToHost, st[0])) == hipSuccess)
             err = hipStreamSynchronize(st[0]);
         if (err != hipSuccess) { g_err = std::string("shard D2H: ") + hipGetErrorString(err); rc = HIPBP_ERR_DEVICE; }
+        else if (*(const uint32_t*)(host + ok_off_h + pad16(B)) != 0) {   // (the blob was parsed: not reached)
+            g_err = "blob decode skipped records of a parsed blob (internal)";
+            rc = HIPBP_ERR_DEVICE;
+        }
     } else {
         (void)hipStreamSynchronize(st[0]);   // nothing in flight reads the staging any more
         if (rc == HIPBP_OK) { g_err = std::string("stream2: ") + hipGetErrorString(s1); rc = HIPBP_ERR_DEVICE; }
     }
     if (gens_ready) (void)hipEventDestroy(gens_ready);
     if (rc == HIPBP_OK)
-        for (size_t k = 0; k < B; k++) ok[idx[k]] = host[ok_off + k] ? 1 : 0;
+        for (size_t k = 0; k < B; k++) ok[src.out_index(k)] = host[ok_off_h + k] ? 1 : 0;
     return rc;
+}
+
+// How the host verifiers read num_gpus: the devices visible (*ndev), the caller's current device
+// (*dev0: shard d runs on device (dev0 + d) % ndev, so num_gpus = 1 stays on it, one rank per GPU in
+// a process group) and the shards (*ng).  HIPBP_HOST_SHARDS=k (tests, only when the caller leaves
+// num_gpus <= 0): k shards (at most 64 and at most one per proof), so the multi-device split, its host
+// threads and the verdict merge also run on a one-GPU box (threads of one device serialise on its
+// engine's mutex).
+int host_verify_devices(size_t count, int num_gpus, int* ng, int* ndev, int* dev0) {
+    BP_RET_ON(hipGetDeviceCount(ndev));
+    if (*ndev <= 0) { g_err = "no HIP device"; return HIPBP_ERR_DEVICE; }
+    if (num_gpus > *ndev) {   // asked for more devices than are visible: an error, not a silent fallback
+        g_err = "num_gpus = " + std::to_string(num_gpus) + " but " + std::to_string(*ndev) + " HIP device(s) visible";
+        return HIPBP_ERR_ARG;
+    }
+    *ng = num_gpus <= 0 ? *ndev : num_gpus;
+    if (num_gpus <= 0)
+        if (const char* hs = getenv("HIPBP_HOST_SHARDS"))
+            if (atoi(hs) > 0) *ng = (int)std::min<size_t>(std::min(atoi(hs), 64), std::max<size_t>(count, 1));
+    BP_RET_ON(hipGetDevice(dev0));
+    return HIPBP_OK;
+}
+// M proofs in contiguous blocks over ng shards, one host thread each: shard(device, lo, hi).  The
+// first failure is reported as "device d: ..." after every thread was joined; the caller's device
+// is restored.
+template <class F>
+int host_verify_fanout(int ng, int ndev, int dev0, size_t M, F shard) {
+    std::vector<int> rcs(ng, HIPBP_OK);
+    std::vector<std::string> errs(ng);
+    std::vector<std::thread> workers;
+    for (int d = 0; d < ng; d++) {
+        const size_t lo = M * d / ng, hi = M * (d + 1) / ng;
+        if (hi == lo) continue;
+        workers.emplace_back([&, d, lo, hi]() {
+            rcs[d] = shard((dev0 + d) % ndev, lo, hi);
+            if (rcs[d] != HIPBP_OK) errs[d] = g_err;   // g_err is per thread
+        });
+    }
+    for (auto& w : workers) w.join();
+    for (int d = 0; d < ng; d++)
+        if (rcs[d] != HIPBP_OK) {
+            g_err = "device " + std::to_string(d) + ": " + errs[d];
+            (void)hipSetDevice(dev0);
+            return rcs[d];
+        }
+    BP_RET_ON(hipSetDevice(dev0));
+    return HIPBP_OK;
+}
+// the shape checks of the device batch (n a power of two, L_len <= log2 n) for a host batch
+int host_verify_shape(size_t n, size_t abl, size_t Lr) {
+    hipbp_proof_batch probe;
+    memset(&probe, 0, sizeof probe);
+    probe.count = 1; probe.n = n; probe.ab_len = abl; probe.L_len = Lr;
+    const uint8_t dummy[1] = {0};
+    probe.V = probe.A = probe.S = probe.T1 = probe.T2 = (const ge25519*)dummy;
+    probe.t = probe.a = probe.b = probe.c = probe.x = (const fe25519*)dummy;
+    probe.L = probe.R = (const ge25519*)dummy;
+    return check_batch(&probe, 1);
 }
 
 }  // namespace
@@ -2391,21 +2561,9 @@ int hipbp_batch_range_proof_verify_host(const RangeProof* proofs, const ge25519*
         g_err = "null argument";
         return HIPBP_ERR_ARG;
     }
-    int ndev = 0;
-    BP_RET_ON(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) { g_err = "no HIP device"; return HIPBP_ERR_DEVICE; }
-    if (num_gpus > ndev) {   // asked for more devices than are visible: an error, not a silent fallback
-        g_err = "num_gpus = " + std::to_string(num_gpus) + " but " + std::to_string(ndev) + " HIP device(s) visible";
-        return HIPBP_ERR_ARG;
-    }
-    int ng = num_gpus <= 0 ? ndev : num_gpus;
-    // HIPBP_HOST_SHARDS=k (tests, only when the caller leaves num_gpus <= 0): k shards (at most 64
-    // and at most one per proof), shard d on device (current + d) % ndev, so the multi-device split, its host
-    // threads and the verdict merge also run on a one-GPU box (threads of one device serialise on
-    // its engine's mutex)
-    if (num_gpus <= 0)
-        if (const char* hs = getenv("HIPBP_HOST_SHARDS"))
-            if (atoi(hs) > 0) ng = (int)std::min<size_t>(std::min(atoi(hs), 64), std::max<size_t>(count, 1));
+    int ng = 0, ndev = 0, dev0 = 0;
+    int rc = host_verify_devices(count, num_gpus, &ng, &ndev, &dev0);
+    if (rc != HIPBP_OK) return rc;
     // The flat batch needs one (a/b length, rounds) shape: the first proof that passes the checks
     // sets it (the reference prover's proofs all share it); proofs of another shape go one by one.
     size_t abl = 0, Lr = 0;
@@ -2424,42 +2582,217 @@ int hipbp_batch_range_proof_verify_host(const RangeProof* proofs, const ge25519*
         if (main.empty()) { abl = ip.a.length; Lr = ip.L_len; }
         (ip.a.length == abl && ip.L_len == Lr ? main : other).push_back(i);
     }
-    if (!main.empty()) {   // the shape checks of the device batch (n a power of two, L_len <= log2 n)
-        hipbp_proof_batch probe;
-        memset(&probe, 0, sizeof probe);
-        probe.count = 1; probe.n = n; probe.ab_len = abl; probe.L_len = Lr;
-        const uint8_t dummy[1] = {0};
-        probe.V = probe.A = probe.S = probe.T1 = probe.T2 = (const ge25519*)dummy;
-        probe.t = probe.a = probe.b = probe.c = probe.x = (const fe25519*)dummy;
-        probe.L = probe.R = (const ge25519*)dummy;
-        int rc = check_batch(&probe, 1);
-        if (rc != HIPBP_OK) return rc;
-    }
-    int dev0 = 0;   // the caller's current device: shard d runs on device (dev0 + d) % ndev, so
-    BP_RET_ON(hipGetDevice(&dev0));   // num_gpus = 1 stays on it (one rank per GPU in a process group)
-    const size_t M = main.size();
-    std::vector<int> rcs(ng, HIPBP_OK);
-    std::vector<std::string> errs(ng);
-    std::vector<std::thread> workers;
-    for (int d = 0; d < ng; d++) {
-        const size_t lo = M * d / ng, hi = M * (d + 1) / ng;
-        if (hi == lo) continue;
-        workers.emplace_back([&, d, lo, hi]() {
-            rcs[d] = host_shard((dev0 + d) % ndev, proofs, V, main.data() + lo, hi - lo, abl, Lr, n, G, H, h, ok);
-            if (rcs[d] != HIPBP_OK) errs[d] = g_err;   // g_err is per thread
-        });
-    }
-    for (auto& w : workers) w.join();
-    for (int d = 0; d < ng; d++)
-        if (rcs[d] != HIPBP_OK) {
-            g_err = "device " + std::to_string(d) + ": " + errs[d];
-            (void)hipSetDevice(dev0);
-            return rcs[d];
-        }
-    BP_RET_ON(hipSetDevice(dev0));
+    if (!main.empty() && (rc = host_verify_shape(n, abl, Lr)) != HIPBP_OK) return rc;
+    rc = host_verify_fanout(ng, ndev, dev0, main.size(), [&](int dev, size_t lo, size_t hi) {
+        return host_shard(dev, StructChunks{proofs, V, main.data() + lo, abl, Lr, n}, hi - lo, n, G, H, nullptr, h, 1, ok);
+    });
+    if (rc != HIPBP_OK) return rc;
     for (size_t i : other)
         ok[i] = verify_single(&proofs[i].ip_proof, &proofs[i], &V[i], nullptr, n, G, H, h) ? 1 : 0;
     return HIPBP_OK;
+}
+
+// ---- compact proof blobs (bp_codec.h, bp_codec.hip)
+}  // extern "C"
+
+namespace {
+
+int codec_fail(const char* what, const char* why) {
+    g_err = std::string(what) + ": " + why;
+    return HIPBP_ERR_ARG;
+}
+// the arrays of one host struct as a one-proof batch (index 0): nothing is copied
+bp::CodecArrays arrays_of_struct(const RangeProof& p) {
+    RangeProof& q = const_cast<RangeProof&>(p);   // (the encoder only reads)
+    bp::CodecArrays A;
+    ge25519* pts[5] = {&q.V, &q.A, &q.S, &q.T1, &q.T2};
+    for (int k = 0; k < 5; k++) A.pt[k] = (bp::ge*)pts[k];
+    A.t = (bp::fe*)&q.t; A.c = (bp::fe*)&q.ip_proof.c; A.x = (bp::fe*)&q.ip_proof.x;
+    A.taux = (bp::fe*)&q.taux; A.mu = (bp::fe*)&q.mu;
+    A.a = (bp::fe*)q.ip_proof.a.elements; A.b = (bp::fe*)q.ip_proof.b.elements;
+    A.L = (bp::ge*)q.ip_proof.L.elements; A.R = (bp::ge*)q.ip_proof.R.elements;
+    return A;
+}
+void free_proof_vectors(RangeProof& p) {
+    free(p.ip_proof.a.elements); free(p.ip_proof.b.elements);
+    free(p.ip_proof.L.elements); free(p.ip_proof.R.elements);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hipbp_proof_blob_bound(size_t count, size_t ab_len, size_t L_len, unsigned flags) {
+    return bp::CodecLayout{count, ab_len, L_len, (int)(flags & 1)}.bound();
+}
+
+int hipbp_proof_blob_header(const uint8_t* header32, size_t blob_bytes, hipbp_proof_blob_info* info) {
+    if (!header32 || !info) return codec_fail("proof_blob_header", "null argument");
+    if (const char* e = bp::codec_parse_header(header32, blob_bytes, info)) return codec_fail("proof_blob_header", e);
+    return HIPBP_OK;
+}
+
+int hipbp_proof_blob_parse(const uint8_t* blob, size_t bytes, hipbp_proof_blob_info* info) {
+    if (!info) return codec_fail("proof_blob_parse", "null argument");
+    if (const char* e = bp::codec_parse(blob, bytes, info)) return codec_fail("proof_blob_parse", e);
+    return HIPBP_OK;
+}
+
+int hipbp_batch_proof_encode(const hipbp_proof_batch* b, int with_blinding, uint8_t* blob_dev, size_t cap,
+                             uint64_t* bytes_out_dev, void* stream) {
+    if (!b || !blob_dev || !bytes_out_dev) return codec_fail("proof_encode", "null argument");
+    if (const char* e = bp::codec_shape_error(b->count, b->n, b->ab_len, b->L_len, 0)) return codec_fail("proof_encode", e);
+    if (b->count && !((b->Vp || b->V) && b->A && b->S && b->T1 && b->T2 && b->t && b->a && b->b && b->c && b->x &&
+                      (!b->L_len || (b->L && b->R))))
+        return codec_fail("proof_encode", "null batch field");
+    if (with_blinding && b->count && (!b->taux || !b->mu)) return codec_fail("proof_encode", "with_blinding needs the batch's taux and mu");
+    if ((uintptr_t)blob_dev % 8) return codec_fail("proof_encode", "blob_dev must be 8-byte aligned");
+    const bp::CodecLayout l{b->count, b->ab_len, b->L_len, with_blinding ? 1 : 0};
+    if (cap < l.bound()) return codec_fail("proof_encode", "cap below hipbp_proof_blob_bound");
+    BP_ENGINE_OR_RET(e);
+    bp::CodecArrays A;
+    const ge25519* pts[5] = {b->Vp ? b->Vp : b->V, b->A, b->S, b->T1, b->T2};
+    for (int k = 0; k < 5; k++) A.pt[k] = (bp::ge*)pts[k];
+    A.t = (bp::fe*)b->t; A.c = (bp::fe*)b->c; A.x = (bp::fe*)b->x; A.a = (bp::fe*)b->a; A.b = (bp::fe*)b->b;
+    A.taux = with_blinding ? (bp::fe*)b->taux : nullptr; A.mu = with_blinding ? (bp::fe*)b->mu : nullptr;
+    A.L = (bp::ge*)b->L; A.R = (bp::ge*)b->R;
+    std::lock_guard<std::mutex> lk(e->mu);
+    Buf(&cb)[bp::CDB_COUNT] = e->streams[pick(stream)].codec;
+    size_t sz[bp::CDB_COUNT];
+    {
+        using namespace bp;
+        const size_t count = b->count;
+        BP_CODEC_BUFS(BP_BUF_SIZE)
+    }
+    // (a grown buffer frees the old one: the stream's earlier encode may still read it)
+    if (sz[bp::CDB_BLK] > cb[bp::CDB_BLK].cap && cb[bp::CDB_BLK].p) BP_RET_ON(hipStreamSynchronize(pick(stream)));
+    BP_RET_ON(need_all(cb, sz));
+    bp::CodecWs w;
+    {
+        using namespace bp;
+        Buf(&b)[CDB_COUNT] = cb;
+        BP_CODEC_BUFS(BP_BUF_FIELD)
+    }
+    bp::launch_codec_encode(A, l, b->n, blob_dev, w, bytes_out_dev, pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_batch_proof_decode(const uint8_t* blob_dev, const hipbp_proof_blob_info* info, hipbp_proof_out* o,
+                             uint32_t* bad_dev, void* stream) {
+    if (!blob_dev || !info || !o || !bad_dev) return codec_fail("proof_decode", "null argument");
+    if (const char* e = bp::codec_shape_error(info->count, info->n, info->ab_len, info->L_len, info->flags))
+        return codec_fail("proof_decode", e);
+    const bp::CodecLayout l = bp::codec_layout(*info);
+    if (info->raw_count > info->count || l.bytes(info->raw_count) != info->bytes || (l.Sc() == 0 && info->raw_count != info->count))
+        return codec_fail("proof_decode", "info does not describe a blob (use hipbp_proof_blob_header)");
+    if ((uintptr_t)blob_dev % 8) return codec_fail("proof_decode", "blob_dev must be 8-byte aligned");
+    if (info->count && !(o->V && o->A && o->S && o->T1 && o->T2 && o->t && o->c && o->x && o->a && o->b &&
+                         (!l.Lr || (o->L && o->R)) && (!l.f || (o->taux && o->mu))))
+        return codec_fail("proof_decode", "null output array");
+    BP_ENGINE_OR_RET(e);
+    (void)e;
+    bp::CodecArrays A;
+    ge25519* pts[5] = {o->V, o->A, o->S, o->T1, o->T2};
+    for (int k = 0; k < 5; k++) A.pt[k] = (bp::ge*)pts[k];
+    A.t = (bp::fe*)o->t; A.c = (bp::fe*)o->c; A.x = (bp::fe*)o->x; A.a = (bp::fe*)o->a; A.b = (bp::fe*)o->b;
+    A.taux = l.f ? (bp::fe*)o->taux : nullptr; A.mu = l.f ? (bp::fe*)o->mu : nullptr;
+    A.L = (bp::ge*)o->L; A.R = (bp::ge*)o->R;
+    BP_RET_ON(hipMemsetAsync(bad_dev, 0, sizeof(uint32_t), pick(stream)));
+    bp::launch_codec_decode(bp::codec_view(blob_dev, info->bytes, l, info->raw_count), A, l, bad_dev, pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_proofs_encode_host(const RangeProof* proofs, size_t count, size_t n, int with_blinding, uint8_t* blob,
+                             size_t cap, size_t* bytes) {
+    if (!blob || !bytes || (count && !proofs)) return codec_fail("proofs_encode_host", "null argument");
+    const size_t abl = count ? proofs[0].ip_proof.a.length : 1, Lr = count ? proofs[0].ip_proof.L_len : 0;
+    for (size_t i = 0; i < count; i++) {
+        const InnerProductProof& ip = proofs[i].ip_proof;
+        if (ip.a.length != abl || ip.b.length != abl || ip.L_len != Lr || ip.L.length < Lr || ip.R.length < Lr ||
+            !ip.a.elements || !ip.b.elements || (Lr && (!ip.L.elements || !ip.R.elements)))
+            return codec_fail("proofs_encode_host", ("proof " + std::to_string(i) +
+                                                     ": another shape than the first proof's, or inconsistent vector lengths").c_str());
+    }
+    if (const char* e = bp::codec_shape_error(count, n, abl, Lr, 0)) return codec_fail("proofs_encode_host", e);
+    const bp::CodecLayout l{count, abl, Lr, with_blinding ? 1 : 0};
+    if (cap < l.bound()) return codec_fail("proofs_encode_host", "cap below hipbp_proof_blob_bound");
+    // the device encoder's three steps, one proof at a time through the same bodies
+    uint8_t* kind = blob + l.o_kind();
+    memset(kind, 0, bp::pad8(count));
+    size_t R = 0;
+    for (size_t i = 0; i < count; i++) R += kind[i] = bp::codec_classify(arrays_of_struct(proofs[i]), l, 0);
+    uint8_t* ridx = blob + l.o_rawidx();
+    memset(ridx, 0, bp::pad8(4 * R));
+    size_t j = 0;
+    for (size_t i = 0; i < count; i++) {
+        const bp::CodecArrays A = arrays_of_struct(proofs[i]);
+        bp::codec_write_compact(blob + l.o_compact() + i * l.Sc(), A, l, 0, kind[i]);
+        if (!kind[i]) continue;
+        bp::put_le(ridx + 4 * j, i, 4);
+        bp::codec_write_raw(blob + l.o_raw(R) + j * l.Sr(), A, l, 0);
+        j++;
+    }
+    bp::codec_write_header(blob, l, n, R);
+    *bytes = l.bytes(R);
+    return HIPBP_OK;
+}
+
+int hipbp_proofs_decode_host(const uint8_t* blob, size_t bytes, RangeProof* proofs) {
+    hipbp_proof_blob_info info;
+    if (const char* e = bp::codec_parse(blob, bytes, &info)) return codec_fail("proofs_decode_host", e);
+    if (info.count == 0) return HIPBP_OK;
+    if (!proofs) return codec_fail("proofs_decode_host", "null proofs");
+    const bp::CodecLayout l = bp::codec_layout(info);
+    const size_t R = info.raw_count;
+    memset(proofs, 0, info.count * sizeof(RangeProof));
+    size_t j = 0, bad = 0, i = 0;
+    bool oom = false;
+    for (; i < info.count && !bad && !oom; i++) {
+        RangeProof& p = proofs[i];
+        if (!bp::proof_vectors_alloc(p.ip_proof, info.n, l.Lr, malloc, l.abl)) { oom = true; i++; break; }
+        const uint8_t k = blob[l.o_kind() + i];
+        bp::BlobView v;
+        v.kind = blob + l.o_kind() + i; v.compact = blob + l.o_compact() + i * l.Sc();
+        v.rawidx = blob + l.o_rawidx() + 4 * j; v.raw = blob + l.o_raw(R) + j * l.Sr();
+        v.count = 1; v.R = k; v.base = i;
+        v.kind_n = v.compact_n = 1; v.rawidx_n = v.raw_n = k;
+        bp::CodecArrays A = arrays_of_struct(p);
+        if (!l.f) A.taux = A.mu = nullptr;
+        bad += bp::codec_decode_cpu(v, A, l);
+        j += k;
+    }
+    if (bad || oom) {   // nothing stays allocated, every struct zero
+        for (size_t k = 0; k < i; k++) free_proof_vectors(proofs[k]);
+        memset(proofs, 0, info.count * sizeof(RangeProof));
+        if (oom) { g_err = "proofs_decode_host: out of memory"; return HIPBP_ERR_DEVICE; }
+        return codec_fail("proofs_decode_host", "a record failed its checks");
+    }
+    return HIPBP_OK;
+}
+
+int hipbp_batch_range_proof_verify_bytes_host(const uint8_t* blob, size_t bytes, const ge25519* V, size_t n,
+                                              const PointVector* G, const PointVector* H, const ge25519* g,
+                                              const ge25519* h, int check, int num_gpus, uint8_t* ok) {
+    const char* me = "range_proof_verify_bytes_host";
+    if (check != 1 && check != 2) return codec_fail(me, "check must be 1 or 2");
+    hipbp_proof_blob_info info;
+    if (const char* e = bp::codec_parse(blob, bytes, &info)) return codec_fail(me, e);   // before anything is uploaded
+    if (info.n != n) return codec_fail(me, "n differs from the blob header's");
+    if (!G || !H || !h || !G->elements || !H->elements || (info.count && !ok)) return codec_fail(me, "null argument");
+    if (G->length != n || H->length != n) return codec_fail(me, "G and H must have n generators");
+    if (check == 2 && !(info.flags & 1)) return codec_fail(me, "check 2 needs a blob with taux and mu");
+    if (check == 2 && !g) return codec_fail(me, "check 2 needs g");
+    if (info.count == 0) return HIPBP_OK;
+    int rc = host_verify_shape(n, info.ab_len, info.L_len);
+    if (rc != HIPBP_OK) return rc;
+    int ng = 0, ndev = 0, dev0 = 0;
+    if ((rc = host_verify_devices(info.count, num_gpus, &ng, &ndev, &dev0)) != HIPBP_OK) return rc;
+    const bp::CodecLayout l = bp::codec_layout(info);
+    return host_verify_fanout(ng, ndev, dev0, info.count, [&](int dev, size_t lo, size_t hi) {
+        return host_shard(dev, BlobChunks{blob, l, info.raw_count, n, lo, V}, hi - lo, n, G, H, g, h, check, ok);
+    });
 }
 
 // ---- cuda_benchmark_* (declared at cuda_bulletproof.h:81-84, never defined by the reference)

@@ -70,18 +70,18 @@ struct ChunkLayout {
 };
 
 // ------------------------------------------------------------------ proof vectors
-// A proof's a, b (length 1) and L, R (Lr points; 1 byte when Lr = 0) malloc'ed as the reference's
+// A proof's a, b (length abl: 1 from the provers) and L, R (Lr points; 1 byte when Lr = 0) malloc'ed as the reference's
 // inner_product_proof_init / field_vector_copy leave them, and n and the lengths set.  False: an
 // allocation failed (what was allocated is in the proof, for the caller to free).  `alloc`: malloc,
 // or what stands in for it in a CPU check.
 typedef void* (*AllocFn)(size_t);
-inline bool proof_vectors_alloc(InnerProductProof& ip, size_t n, size_t Lr, AllocFn alloc = malloc) {
-    ip.a.elements = (fe25519*)alloc(FE);
-    ip.b.elements = (fe25519*)alloc(FE);
+inline bool proof_vectors_alloc(InnerProductProof& ip, size_t n, size_t Lr, AllocFn alloc = malloc, size_t abl = 1) {
+    ip.a.elements = (fe25519*)alloc(abl * FE);
+    ip.b.elements = (fe25519*)alloc(abl * FE);
     ip.L.elements = (ge25519*)alloc(Lr ? Lr * GE : 1);
     ip.R.elements = (ge25519*)alloc(Lr ? Lr * GE : 1);
     ip.n = n;
-    ip.a.length = ip.b.length = 1;
+    ip.a.length = ip.b.length = abl;
     ip.L.length = ip.R.length = ip.L_len = Lr;
     return ip.a.elements && ip.b.elements && ip.L.elements && ip.R.elements;
 }
@@ -245,6 +245,15 @@ inline size_t commit_chunk(size_t count, long long env) {
     size_t ch = env > 0 ? (size_t)env : COMMIT_CHUNK;
     if (ch > COMMIT_CHUNK_MAX) ch = COMMIT_CHUNK_MAX;
     return count < ch ? count : ch;
+}
+
+// The proof blob encoder (CodecWs, bp_codec.h) for `count` proofs: one raw count per block of 256
+// proofs, and the total after them.
+#define BP_CODEC_BUFS(X) X(CDB_BLK, blk, uint32_t, (codec_blocks(count) + 1) * U32)
+enum CodecBuf { BP_CODEC_BUFS(BP_BUF_ID) CDB_COUNT };
+inline size_t codec_blocks(size_t count) { return (count + 255) / 256; }
+inline void codec_sizes(size_t count, size_t (&sz)[CDB_COUNT]) {
+    BP_CODEC_BUFS(BP_BUF_SIZE)
 }
 
 // A verify slot (VerifyWs) for B proofs of n bits with Lb fold rounds; Lc = max(Lb, 1); m2 = B in mode 2

@@ -486,6 +486,91 @@ int hipbp_inner_product_prove_host(InnerProductProof* proof, const FieldVector* 
                                    const PointVector* G, const PointVector* H, const ge25519* Q,
                                    const fe25519* c_in, const uint8_t* transcript32 /* NULL = zeros */);
 
+/* ---- compact proof blobs (no reference counterpart): a batch of range proofs as one byte string, to
+ * store or send ("HBPC", version 1).  The reference's points are not on a curve, so there
+ * is no 32-byte point encoding; but every point its prover writes went through ge25519_normalize (Z
+ * limbs (1, 0, 0, 0), T = fe25519_mul(X, Y)) and fix_inner_product_proof leaves a = [t], b = [1],
+ * c = t, so Z, T, a, b and c are dropped and recomputed bit for bit.  A proof where any of that does
+ * not hold limb for limb (never mod p: a Z of p + 1, a T off in one limb, a b of 1 + p) is stored
+ * verbatim, so decode(encode(x)) = x for any limbs.  All integers little-endian, a field element is
+ * its four limbs as stored (32 bytes); Lr = L_len, f = 1 when the records carry taux and mu:
+ *   0  u8[4] "HBPC"   4  u16 version = 1   6  u16 flags (bit 0 = f, others 0)
+ *   8  u32 n         12  u32 ab_len       16  u32 L_len    20  u32 raw_count R    24  u64 count
+ *   32 kind[count]   u8: 0 compact, 1 raw; zero-padded to a multiple of 8 bytes
+ *      compact area  count slots of S_c bytes; slot i all zero when kind[i] = 1
+ *      raw_index[R]  u32, strictly ascending: the proofs of kind 1; zero-padded to a multiple of 8 bytes
+ *      raw area      R records of S_r bytes; record j belongs to proof raw_index[j]
+ *   compact slot, S_c = 64 (5 + 2 Lr) + 64 + 64 f (0 when ab_len != 1: every proof is then raw):
+ *      X | Y of V, A, S, T1, T2, L[0..Lr), R[0..Lr); t, x; taux, mu if f
+ *   raw record, S_r = 128 (5 + 2 Lr) + 96 + 64 f + 64 ab_len:
+ *      the same points whole; t, c, x; taux, mu if f; a[ab_len]; b[ab_len]
+ * n = 64, Lr = 6, f = 1: S_c = 1216 against the 2400 bytes of S_r.  The blob is a function of the
+ * proofs alone: the CPU and the GPU encoder give identical bytes.  Limits: count <= 2^22, n a power of
+ * two <= 65536, L_len <= log2 n, ab_len >= 1.  The V encoded is the batch's Vp when non-NULL, else V. */
+typedef struct {
+    size_t count, n, ab_len, L_len;
+    unsigned flags;      /* bit 0: the records carry taux and mu */
+    size_t raw_count;    /* R */
+    size_t bytes;        /* the blob's exact size */
+} hipbp_proof_blob_info;
+/* The size of a blob of `count` proofs when every one is raw: what an encoder's buffer must hold. */
+size_t hipbp_proof_blob_bound(size_t count, size_t ab_len, size_t L_len, unsigned flags);
+/* Validates a HOST copy of a blob's 32 header bytes (magic, version, flags, the limits, R <= count)
+ * and that the sections the header implies make exactly blob_bytes; fills *info.  For blobs that
+ * live in device memory: hipbp_batch_proof_decode takes the info.  HIPBP_ERR_ARG with a message. */
+int hipbp_proof_blob_header(const uint8_t* header32, size_t blob_bytes, hipbp_proof_blob_info* info);
+/* Fully validates a HOST blob: the header as above, every kind <= 1, R equal to the number of kind-1
+ * bytes, raw_index strictly ascending and naming exactly those proofs, zero padding and zero slots
+ * of raw proofs.  Anything wrong: HIPBP_ERR_ARG with a message, *info undefined.  No HIP call. */
+int hipbp_proof_blob_parse(const uint8_t* blob, size_t bytes, hipbp_proof_blob_info* info);
+/* Encodes a device batch into blob_dev (DEVICE, 8-byte aligned, `cap` bytes) and writes the blob's
+ * size to *bytes_out_dev (DEVICE).  with_blinding != 0 (f = 1) needs the batch's taux and mu.
+ * Three launches: classify (one lane per point), a one-block scan of the per-block raw counts, and
+ * the write (compact slots, the raw proofs ranked in index order, padding, header); no step's
+ * result depends on timing.  A cap below hipbp_proof_blob_bound, a bad shape or a null pointer give
+ * HIPBP_ERR_ARG and enqueue nothing.  count = 0 gives the 32-byte header.  Asynchronous on `stream`;
+ * the block counts live in a workspace kept per (device, stream), freed by
+ * hipbp_release_stream_workspaces. */
+int hipbp_batch_proof_encode(const hipbp_proof_batch* batch, int with_blinding, uint8_t* blob_dev, size_t cap,
+                             uint64_t* bytes_out_dev, void* stream);
+/* Decodes a DEVICE blob (8-byte aligned) whose header the host validated into *info
+ * (hipbp_proof_blob_header) into out's arrays (hipbp_proof_out's layout with a, b of count ab_len
+ * elements and L, R of count L_len; out->valid is ignored; taux, mu may be NULL when f = 0; c is
+ * written).  One launch over the compact slots (T recomputed), one over the R raw records.  Every
+ * index read from the blob is checked against the header and info->bytes before use; a record that
+ * fails is skipped and counted: *bad_dev (DEVICE, set by the call) = the number skipped, 0 for a
+ * blob hipbp_proof_blob_parse accepts.  Asynchronous on `stream`. */
+int hipbp_batch_proof_decode(const uint8_t* blob_dev, const hipbp_proof_blob_info* info, hipbp_proof_out* out,
+                             uint32_t* bad_dev, void* stream);
+/* The encoder on the reference's host structs, on the CPU: no HIP call, no device needed; the bytes
+ * are the device encoder's.  The first proof sets ab_len (a.length) and L_len; a proof of another
+ * shape, or with b.length != a.length, L or R shorter than L_len, or a missing vector, gives
+ * HIPBP_ERR_ARG naming its index, as does a cap below hipbp_proof_blob_bound; nothing is written
+ * then.  with_blinding != 0 stores each proof's taux and mu.  *bytes = the blob's size. */
+int hipbp_proofs_encode_host(const RangeProof* proofs, size_t count, size_t n, int with_blinding, uint8_t* blob,
+                             size_t cap, size_t* bytes);
+/* The decoder into host structs, on the CPU: parses the blob (hipbp_proof_blob_parse), then fills
+ * proofs[0 .. count) as hipbp_batch_generate_range_proof_host leaves valid proofs: ip_proof.n = n, a
+ * and b of ab_len, L and R of L_len, all malloc'ed, so range_proof_free frees them; taux and mu are
+ * zero when f = 0.  On any error nothing stays allocated; every struct is zero, except where the blob
+ * does not parse: its count is not known then and proofs is left untouched. */
+int hipbp_proofs_decode_host(const uint8_t* blob, size_t bytes, RangeProof* proofs);
+/* Verifies a HOST blob on the GPU(s), uploading the blob's bytes instead of the structs'.
+ * check 1: cuda_range_proof_verify semantics, ok[i] = hipbp_batch_range_proof_verify_host on the
+ * decoded structs; check 2: range_proof_verify semantics (needs f = 1 and g), ok[i] =
+ * hipbp_batch_range_proof_verify_std on the decoded batch.  V (HOST, [count]) is the caller's V
+ * argument; NULL: each proof's own V.  The blob is parsed on the host before anything is uploaded;
+ * n != the header's n, a shape the pipelines cannot take, a bad check: HIPBP_ERR_ARG, nothing
+ * verified.  Sharding as hipbp_batch_range_proof_verify_host (contiguous blocks over num_gpus,
+ * HIPBP_HOST_SHARDS, the device restored, errors as "device d: ...").  Per 1024-proof chunk a shard
+ * uploads that chunk's kind bytes, its compact slots and its raw records (found by binary search in
+ * raw_index), decodes them on the chunk's stream into a flat device chunk and pushes it, alternating
+ * over two pipelines.  check 1 uses the cached host prefix tables (HIPBP_HOST_PREFIX_BITS) as
+ * _verify_host does; check 2 runs without tables.  Synchronous. */
+int hipbp_batch_range_proof_verify_bytes_host(const uint8_t* blob, size_t bytes, const ge25519* V, size_t n,
+                                              const PointVector* G, const PointVector* H, const ge25519* g,
+                                              const ge25519* h, int check, int num_gpus, uint8_t* ok);
+
 /* Canonical-tree MSM on device buffers.  Asynchronous on `stream`; the MSM, MSM-batch
  * and point-tree calls keep one workspace per (device, stream), so calls on different streams may
  * run concurrently. */
@@ -563,7 +648,7 @@ int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, voi
  * gated forms); the results are the same bits either way.  For tests. */
 int hipbp_sm_probe(int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count, void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
- * point-tree, prover, the Pedersen commitments' terms, the seeded prover's scalars and keys, the accepted prover's retry workspace, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
+ * point-tree, prover, the Pedersen commitments' terms, the seeded prover's scalars and keys, the accepted prover's retry workspace, the proof blob encoder's block counts, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
  * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
  * a caller that makes short-lived streams calls this before destroying one.  No reference
  * counterpart. */
