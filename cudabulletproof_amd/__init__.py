@@ -125,7 +125,7 @@ EXPORTS = [
     "hipbp_batch_range_proof_verify_std", "hipbp_batch_range_proof_verify_gens", "hipbp_batch_inner_product_verify", "hipbp_batch_generate_range_proof", "hipbp_msm",
     "hipbp_msm_pippenger", "hipbp_msm_pippenger_batch", "hipbp_msm_pippenger_windows",
     "hipbp_msm_pippenger_horner", "hipbp_msm_batch", "hipbp_msm_batch_gens", "hipbp_point_tree", "hipbp_field_op",
-    "hipbp_sha_probe", "hipbp_sm_probe", "hipbp_sync", "hipbp_timing_enable",
+    "hipbp_sha_probe", "hipbp_sm_probe", "hipbp_sm_form_probe", "hipbp_sync", "hipbp_timing_enable",
     "hipbp_timing_collect", "hipbp_kernel_count", "hipbp_kernel_name", "hipbp_pipeline_create",
     "hipbp_pipeline_push", "hipbp_pipeline_flush", "hipbp_pipeline_depth", "hipbp_pipeline_destroy",
     "hipbp_pipeline_defer_msm",
@@ -166,7 +166,8 @@ def lib():
                   "hipbp_batch_inner_product_verify", "hipbp_batch_generate_range_proof", "hipbp_msm",
                   "hipbp_msm_pippenger", "hipbp_msm_pippenger_batch", "hipbp_msm_pippenger_windows",
                   "hipbp_msm_pippenger_horner", "hipbp_msm_batch", "hipbp_msm_batch_gens", "hipbp_point_tree",
-                  "hipbp_field_op", "hipbp_sha_probe", "hipbp_sm_probe", "hipbp_sync", "hipbp_device_count",
+                  "hipbp_field_op", "hipbp_sha_probe", "hipbp_sm_probe", "hipbp_sm_form_probe", "hipbp_sync",
+                  "hipbp_device_count",
                   "hipbp_release_stream_workspaces", "hipbp_batch_inner_product_prove",
                   "hipbp_batch_inner_product_prove_gens", "hipbp_inner_product_prove_host",
                   "hipbp_derive_prover_scalars", "hipbp_batch_generate_range_proof_seeded",
@@ -1114,6 +1115,15 @@ def sm_probe(force, out, scalars, points, stream=None):
     points; force: through the deferred pass's recovery path (the same bits)."""
     _chk(lib().hipbp_sm_probe(int(bool(force)), _c(out.data_ptr()), _c(scalars.data_ptr()), _c(points.data_ptr()),
                               _sz(scalars.shape[0]), _stream_ptr(stream)))
+
+
+def sm_form_probe(form, force, out, scalars, points, stream=None):
+    """hipbp_sm_form_probe: the same through the drain-tick forms, form 1 lane quads (sm_quad), 2 lane pairs
+    (sm_pair), 3 16-lane rows (sm_row); force = 1 (form 3 only): every step through the row step's deferred
+    recompute (the same bits).  form and force go to the library as given: it refuses any other value."""
+    _chk(lib().hipbp_sm_form_probe(ctypes.c_int(int(form)), ctypes.c_int(int(force)), _c(out.data_ptr()),
+                                   _c(scalars.data_ptr()), _c(points.data_ptr()), _sz(scalars.shape[0]),
+                                   _stream_ptr(stream)))
 
 
 def sha_probe(kind, out, inp, stream=None):

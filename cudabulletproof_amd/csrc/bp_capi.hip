@@ -2048,6 +2048,21 @@ int hipbp_sm_probe(int force, ge25519* out, const fe25519* scalars, const ge2551
     return HIPBP_OK;
 }
 
+int hipbp_sm_form_probe(int form, int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count,
+                        void* stream) {
+    BP_ENGINE_OR_RET(e);
+    if (form < 1 || form > 3) { g_err = "sm_form_probe: form must be 1 (quads), 2 (pairs) or 3 (rows)"; return HIPBP_ERR_ARG; }
+    if (force != 0 && force != 1) { g_err = "sm_form_probe: force must be 0 or 1"; return HIPBP_ERR_ARG; }
+    if (force && form != 3) { g_err = "sm_form_probe: force = 1 needs form 3 (only the row form has a recompute)"; return HIPBP_ERR_ARG; }
+    if (count > ((size_t)1 << 31)) { g_err = "sm_form_probe: count above 2^31"; return HIPBP_ERR_ARG; }
+    if (count == 0) return HIPBP_OK;
+    if (!out || !scalars || !points) { g_err = "null operand"; return HIPBP_ERR_ARG; }
+    bp::launch_sm_form_probe(form, force != 0, (bp::ge*)out, (const bp::fe*)scalars, (const bp::ge*)points, count, e->dtab,
+                             pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
 int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, void* stream) {
     BP_ENGINE_OR_RET(e);
     if (kind < 0 || kind > 5) { g_err = "bad sha probe kind"; return HIPBP_ERR_ARG; }

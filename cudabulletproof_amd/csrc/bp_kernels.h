@@ -388,6 +388,10 @@ void launch_field_op(int op, fe* r, const fe* a, const fe* b, size_t count, hipS
 void launch_sha_probe(int kind, fe* out, const fe* in, size_t count, hipStream_t s);
 // out[i] = scalarmult(s[i], P[i]) (raw); force: through the deferred pass's recovery path
 void launch_sm_probe(int force, ge* out, const fe* s, const ge* P, size_t count, const ge* dtab, hipStream_t st);
+// the same through sm_quad (form 1), sm_pair (2) or sm_row (3; force: every step through its deferred
+// recompute), item i on lanes [L i, L i + L) for L = 4, 2, 16; count * L < 2^32 * TPB
+void launch_sm_form_probe(int form, bool force, ge* out, const fe* s, const ge* P, size_t count, const ge* dtab,
+                          hipStream_t st);
 void launch_ip_shared(fe* out, const fe* a, const fe* b, size_t n, hipStream_t s);
 void launch_ip_grid(fe* out, fe* part, const fe* a, const fe* b, size_t n, hipStream_t s);
 void launch_ip_batch(fe* out, const fe* a, const fe* b, size_t n, size_t nvec, hipStream_t s);

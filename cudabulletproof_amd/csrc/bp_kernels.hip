@@ -488,6 +488,37 @@ void launch_sm_probe(int force, ge* out, const fe* s, const ge* P, size_t count,
     k_sm_probe<<<nblk(count), TPB, 0, st>>>(force, out, s, P, count, dtab);
 }
 
+// The drain-tick forms of the same function, through the calls k_terms<4 / 2 / 16> make (ge25519_quad.h
+// sm_quad / sm_pair / sm_row with the engine's dtab and no prefix table): item i on the QL lanes
+// [QL i, QL i + QL) of the grid, its scalar and point replicated over them as k_terms<QL> does; the item's
+// first lane stores the raw extended result.  TPB and the wave are multiples of QL, so an item has all of
+// its lanes or none: the items past `count` in the last wave stay out whole, as k_terms' dead lanes do.
+// FORCE (rows only): every step of every chain through the deferred recompute (sm_row<true>); the same
+// bits either way (hipbp_sm_form_probe, tests/test_sm_forms_gpu.py).
+template <int QL, bool FORCE>
+__global__ __launch_bounds__(TPB) void k_sm_form_probe(ge* out, const fe* __restrict__ s, const ge* __restrict__ P,
+                                                       size_t count, const ge* __restrict__ dtab) {
+    static_assert(TPB % QL == 0 && 64 % QL == 0 && (!FORCE || QL == 16), "whole items per wave; FORCE is the row form's");
+    const size_t i = gid() / QL;
+    if (i >= count) return;
+    ge t;
+    if (QL == 16) t = sm_row<FORCE>(s[i], P[i], dtab, nullptr, 0);
+    else if (QL == 4) t = sm_quad(s[i], P[i], dtab, nullptr, 0);
+    else t = sm_pair(s[i], P[i], dtab, nullptr, 0);
+    if ((threadIdx.x & (QL - 1)) == 0) out[i] = t;
+}
+
+void launch_sm_form_probe(int form, bool force, ge* out, const fe* s, const ge* P, size_t count, const ge* dtab,
+                          hipStream_t st) {
+    if (count == 0) return;
+    const int ql = form == 1 ? 4 : form == 2 ? 2 : 16;   // HIPBP_QUAD's values: 1 quads, 2 pairs, 3 rows
+    const unsigned blocks = nblk(count * ql);
+    if (ql == 4) k_sm_form_probe<4, false><<<blocks, TPB, 0, st>>>(out, s, P, count, dtab);
+    else if (ql == 2) k_sm_form_probe<2, false><<<blocks, TPB, 0, st>>>(out, s, P, count, dtab);
+    else if (force) k_sm_form_probe<16, true><<<blocks, TPB, 0, st>>>(out, s, P, count, dtab);
+    else k_sm_form_probe<16, false><<<blocks, TPB, 0, st>>>(out, s, P, count, dtab);
+}
+
 void launch_sha_probe(int kind, fe* out, const fe* in, size_t count, hipStream_t s) {
     if (count == 0) return;
     k_sha_probe<<<nblk(count), TPB, 0, s>>>(kind, out, in, count);

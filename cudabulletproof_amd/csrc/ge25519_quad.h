@@ -290,6 +290,9 @@ __device__ __forceinline__ ge row_of_point(const fe& r3) {   // X3 | T3 | Z3 | Y
 #ifndef BP_ROW_CTRL
 #define BP_ROW_CTRL 1
 #endif
+// FORCE (the probe's recompute mode, hipbp_sm_form_probe): every step takes the deferred recompute whatever
+// the data, as BP_ROW_DEFER_FORCE does for a whole build; the call sites of the kernels keep the default.
+template <bool FORCE = false>
 __device__ __forceinline__ ge sm_row(const fe& s, const ge& P, const ge* __restrict__ dtab, const ge* ptab, int K) {
     const fe qs = row_of_form(P);
     int i;   // index of the pending bit
@@ -316,7 +319,7 @@ __device__ __forceinline__ ge sm_row(const fe& s, const ge& P, const ge* __restr
             const fe qq = fe_sel(add_phase, qs, o);
             uint32_t acc = 0;
             r3 = ge_row_of_step<2>(o, qq, &acc);
-            if (BP_ROW_DEFER_FORCE || __builtin_expect(__builtin_amdgcn_ballot_w64(acc == 0xFFFFFFFFu) != 0, 0))
+            if (FORCE || BP_ROW_DEFER_FORCE || __builtin_expect(__builtin_amdgcn_ballot_w64(acc == 0xFFFFFFFFu) != 0, 0))
                 r3 = ge_row_of_step<BP_ROW_LAT>(o, qq);
         }
 #else

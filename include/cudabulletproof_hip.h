@@ -647,6 +647,16 @@ int hipbp_sha_probe(int kind, fe25519* out, const fe25519* in, size_t count, voi
  * first chunk of steps whatever the data, so the call takes the recovery path (the rerun with the
  * gated forms); the results are the same bits either way.  For tests. */
 int hipbp_sm_probe(int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count, void* stream);
+/* The same function through the drain-tick forms, by the calls the verify kernels make: form takes
+ * HIPBP_QUAD's values, 1 a lane quad per item (sm_quad), 2 a lane pair (sm_pair), 3 a 16-lane row (sm_row,
+ * the form of every cuda_range_proof_verify call); no prefix table.  Item i occupies lanes [L i, L i + L) of
+ * the grid, L = 4, 2, 16, its scalar and point replicated over them; the items past count in the last wave
+ * stay out whole.  force = 1 (form 3 only): every step of every chain takes the row step's deferred
+ * recompute whatever the data; the results are the same bits either way.  Any other form or force, and
+ * force = 1 with form 1 or 2, is HIPBP_ERR_ARG with a message and launches nothing; count = 0 is a no-op.
+ * For tests. */
+int hipbp_sm_form_probe(int form, int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count,
+                        void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
  * point-tree, prover, the Pedersen commitments' terms, the seeded prover's scalars and keys, the accepted prover's retry workspace, the proof blob encoder's block counts, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
  * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
