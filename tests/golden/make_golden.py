@@ -41,7 +41,9 @@ oracle/build_ref.sh) and records inputs + reference outputs as .npz (no pickles)
               inner_product_prove cases (n = 1, 8; projective G, H, Q) with their inputs, in
               ipa_prove.npz's layout under the prefix ipa_.
 
-  python tests/golden/make_golden.py [ipa4096|rpverify|accept|printed|batch1024|projective]
+  scalar_edges.npz ge25519_scalarmult of h by the raw bytes of tests/prove_edges.py's edge list E (20 rows).
+
+  python tests/golden/make_golden.py [ipa4096|rpverify|accept|printed|batch1024|projective|scalar_edges]
               (argument: regenerate only that fixture)
 
 The survey's golden digests are reproduced by tests/test_oracle_golden.py.
@@ -591,8 +593,25 @@ def make_projective():
           f"ipa ok_in {out['ipa_ok_in'].tolist()} ok_final {out['ipa_ok_final'].tolist()}")
 
 
+def make_scalar_edges():
+    """scalar_edges.npz: the reference's ge25519_scalarmult of h by the raw 32 bytes of each value of the edge
+    list E of tests/prove_edges.py (0, short scalars, p and 2p and their neighbours, bit 255 set, all ones): how
+    the prover's h^alpha and h^rho treat bytes that are no masked random scalar."""
+    po.build()
+    R = po.Reference()
+    sys.path.insert(0, os.path.dirname(HERE))
+    import prove_edges as pe
+    _, h = R.gh()
+    sc = np.stack([pe.b32(e) for e in pe.E])
+    sm = np.stack([R.ge_op("ge_scalarmult", sc[i], h) for i in range(len(sc))])
+    np.savez_compressed(os.path.join(HERE, "scalar_edges.npz"), h=h, scalars=sc, scalarmult=sm)
+    print(f"scalar_edges: {len(sc)} rows, {len({bytes(r) for r in sm})} distinct results")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["projective"]:
+    if sys.argv[1:] == ["scalar_edges"]:
+        make_scalar_edges()
+    elif sys.argv[1:] == ["projective"]:
         make_projective()
     elif sys.argv[1:] == ["batch1024"]:
         make_batch1024()

@@ -45,6 +45,17 @@ def test_points_against_reference(oracle, golden):
         assert np.array_equal(oracle.ge_scalarmult(d["scalars"][i], d["p"][i]), d["scalarmult"][i]), i
 
 
+def test_scalar_edges_against_reference(oracle, golden):
+    """ge_scalarmult of h by the raw bytes of every value of tests/prove_edges.py's edge list (0, short scalars,
+    p, 2p, bit 255 set, all ones): the rows the prover tests' h^alpha and h^rho expectations rest on."""
+    import prove_edges as pe
+    d = golden("scalar_edges")
+    assert np.array_equal(d["h"], oracle.gh()[1])
+    assert np.array_equal(d["scalars"], np.stack([pe.b32(e) for e in pe.E]))
+    for i in range(len(d["scalars"])):
+        assert np.array_equal(oracle.ge_scalarmult(d["scalars"][i], d["h"]), d["scalarmult"][i]), pe.name(pe.E[i])
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 16, 17, 64])
 def test_msm_against_reference(oracle, golden, n):
     d = golden("msm")
