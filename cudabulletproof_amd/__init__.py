@@ -24,7 +24,8 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libcudabulletproof_hip.so")
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["bp_terms1.hip", "bp_terms2.hip", "bp_terms4.hip", "bp_terms16.hip", "bp_kernels.hip", "bp_prove.hip",
-           "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_commit.hip", "bp_codec.hip", "bp_capi.hip"]
+           "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_commit.hip", "bp_codec.hip", "bp_ids.hip",
+           "bp_capi.hip"]
 
 _lib = None
 
@@ -141,6 +142,8 @@ EXPORTS = [
     "hipbp_proof_blob_bound", "hipbp_proof_blob_header", "hipbp_proof_blob_parse", "hipbp_batch_proof_encode",
     "hipbp_batch_proof_decode", "hipbp_proofs_encode_host", "hipbp_proofs_decode_host",
     "hipbp_batch_range_proof_verify_bytes_host",
+    "hipbp_batch_proof_ids", "hipbp_blob_proof_ids", "hipbp_merkle_root", "hipbp_proof_ids_host",
+    "hipbp_blob_proof_ids_host", "hipbp_merkle_root_host", "hipbp_merkle_path_host", "hipbp_merkle_verify_host",
 ]
 
 
@@ -178,7 +181,10 @@ def lib():
                   "hipbp_batch_pedersen_commit", "hipbp_batch_pedersen_commit_gens", "hipbp_batch_pedersen_open",
                   "hipbp_batch_pedersen_commit_host", "hipbp_proof_blob_header", "hipbp_proof_blob_parse",
                   "hipbp_batch_proof_encode", "hipbp_batch_proof_decode", "hipbp_proofs_encode_host",
-                  "hipbp_proofs_decode_host", "hipbp_batch_range_proof_verify_bytes_host"):
+                  "hipbp_proofs_decode_host", "hipbp_batch_range_proof_verify_bytes_host",
+                  "hipbp_batch_proof_ids", "hipbp_blob_proof_ids", "hipbp_merkle_root", "hipbp_proof_ids_host",
+                  "hipbp_blob_proof_ids_host", "hipbp_merkle_root_host", "hipbp_merkle_path_host",
+                  "hipbp_merkle_verify_host"):
             getattr(L, f).restype = ctypes.c_int
         L.hipbp_proof_blob_bound.restype = ctypes.c_size_t
         _lib = L
@@ -915,6 +921,135 @@ def decode_proofs(blob_tensor, stream=None):
         raise BulletproofError(f"decode_proofs: {int(bad.item())} record(s) failed their checks and were skipped")
     del out["valid"]
     return RangeProofBatch(n, **out)
+
+
+# ---------------------------------------------------------------------- proof ids and the batch Merkle root
+def proof_ids(batch, with_blinding=False, stream=None, return_kinds=False):
+    """hipbp_batch_proof_ids: the id of every proof of a RangeProofBatch, on its device: a (B, 32) uint8
+    CUDA tensor (SHA-256 of a 32-byte header and the record the compact blob stores for
+    the proof).  with_blinding needs batch.taux / batch.mu and gives other ids.  return_kinds: also
+    the (B,) uint8 kinds (0 compact, 1 raw).  Asynchronous on `stream`."""
+    import contextlib
+
+    import torch
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        ids = torch.empty(batch.count, 32, dtype=torch.uint8, device=batch.V.device)
+        kinds = torch.empty(batch.count, dtype=torch.uint8, device=batch.V.device) if return_kinds else None
+    s = batch.c_struct()
+    _chk(lib().hipbp_batch_proof_ids(ctypes.byref(s), ctypes.c_int(1 if with_blinding else 0), _c(ids.data_ptr()),
+                                     _c(kinds.data_ptr()) if return_kinds else None, _stream_ptr(stream)))
+    return (ids, kinds) if return_kinds else ids
+
+
+def blob_proof_ids(blob_tensor, stream=None):
+    """hipbp_blob_proof_ids: the ids of the proofs of a blob in a uint8 CUDA tensor -> (ids (B, 32)
+    uint8, bad), both on its device.  The 32 header bytes are read back and validated on the host; the
+    kernel checks every index it takes from the blob: a record that fails has an all-zero id and is
+    counted in bad (a 1-element int32 tensor; 0 for a well-formed blob).  Asynchronous on `stream`
+    after the header's read-back."""
+    import contextlib
+
+    import torch
+    blob_tensor = blob_tensor.contiguous()
+    if blob_tensor.dtype != torch.uint8 or blob_tensor.dim() != 1:
+        raise ValueError("blob_tensor must be a 1-D uint8 tensor")
+    head = blob_tensor[:32].cpu().numpy()
+    if len(head) < 32:
+        raise BulletproofError("proof_blob_header: blob shorter than its header")
+    ic = ProofBlobInfoC()
+    _chk(lib().hipbp_proof_blob_header(_p(head), _sz(blob_tensor.numel()), ctypes.byref(ic)))
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        ids = torch.empty(int(ic.count), 32, dtype=torch.uint8, device=blob_tensor.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=blob_tensor.device)
+    _chk(lib().hipbp_blob_proof_ids(_c(blob_tensor.data_ptr()), ctypes.byref(ic), _c(ids.data_ptr()), _c(bad.data_ptr()),
+                                    _stream_ptr(stream)))
+    return ids, bad
+
+
+def merkle_root(ids, stream=None):
+    """hipbp_merkle_root: the RFC 6962 Merkle root over a (B, 32) uint8 CUDA tensor of ids (the ids are
+    the leaf inputs; B = 0: SHA-256 of the empty string) -> a (32,) uint8 tensor on its device.
+    Asynchronous on `stream`."""
+    import contextlib
+
+    import torch
+    ids = ids.contiguous()
+    if ids.dtype != torch.uint8 or ids.dim() != 2 or ids.shape[1] != 32:
+        raise ValueError("ids must be a (B, 32) uint8 tensor")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        root = torch.empty(32, dtype=torch.uint8, device=ids.device)
+    _chk(lib().hipbp_merkle_root(_c(ids.data_ptr()) if ids.shape[0] else None, _sz(ids.shape[0]), _c(root.data_ptr()),
+                                 _stream_ptr(stream)))
+    return root
+
+
+def _ids_arg(ids):
+    """A list of 32-byte ids, or a (B, 32) uint8 array, as a contiguous (B, 32) uint8 array."""
+    if isinstance(ids, np.ndarray):
+        a = np.ascontiguousarray(ids, np.uint8)
+    else:
+        ids = [bytes(i) for i in ids]
+        if any(len(i) != 32 for i in ids):
+            raise ValueError("an id is 32 bytes")
+        a = np.frombuffer(b"".join(ids), np.uint8)
+    return a.reshape(-1, 32)
+
+
+def _ids_list(a, count):
+    return [a[32 * i:32 * i + 32].tobytes() for i in range(count)]
+
+
+def proof_ids_host(proofs, n, with_blinding=False):
+    """hipbp_proof_ids_host: the ids of a list of proof dicts (what proofs_to_bytes takes), as a list of
+    32-byte `bytes`: proof_ids' bytes.  CPU only: needs no GPU."""
+    keep = []
+    count = len(proofs)
+    arr = (RangeProofC * max(count, 1))()
+    for i, pr in enumerate(proofs):
+        arr[i] = _range_proof_struct(pr, n, keep)
+    out = np.zeros(32 * max(count, 1), np.uint8)
+    _chk(lib().hipbp_proof_ids_host(arr, _sz(count), _sz(int(n)), ctypes.c_int(1 if with_blinding else 0), _p(out)))
+    return _ids_list(out, count)
+
+
+def blob_proof_ids_host(blob):
+    """hipbp_blob_proof_ids_host: the ids of the proofs of a host blob (fully parsed first; a malformed
+    one raises BulletproofError), as a list of 32-byte `bytes`.  CPU only: needs no GPU."""
+    b = _blob_arg(blob)
+    count = proof_blob_info(b)["count"]
+    out = np.zeros(32 * max(count, 1), np.uint8)
+    _chk(lib().hipbp_blob_proof_ids_host(_p(b), _sz(len(b)), _p(out)))
+    return _ids_list(out, count)
+
+
+def merkle_root_host(ids):
+    """hipbp_merkle_root_host: the Merkle root over the ids (a list of 32-byte ids or a (B, 32) uint8
+    array) as 32 `bytes`.  CPU only."""
+    a = _ids_arg(ids)
+    root = np.zeros(32, np.uint8)
+    _chk(lib().hipbp_merkle_root_host(_p(a) if len(a) else None, _sz(len(a)), _p(root)))
+    return root.tobytes()
+
+
+def merkle_path(ids, index):
+    """hipbp_merkle_path_host: the RFC 6962 audit path of ids[index], bottom-up, as a list of 32-byte
+    `bytes`.  CPU only."""
+    a = _ids_arg(ids)
+    path = np.zeros(32 * 22, np.uint8)
+    n = _sz(0)
+    _chk(lib().hipbp_merkle_path_host(_p(a) if len(a) else None, _sz(len(a)), _sz(int(index)), _p(path), ctypes.byref(n)))
+    return _ids_list(path, n.value)
+
+
+def merkle_verify(id, index, count, path, root):
+    """hipbp_merkle_verify_host: True when (id, index, count, path) recomputes `root`, consuming exactly
+    the path's entries.  CPU only."""
+    i, r = _ids_arg([id]), _ids_arg([root])
+    p = _ids_arg(path)
+    if index < 0 or count < 0:
+        return False
+    return bool(lib().hipbp_merkle_verify_host(_p(i), _sz(int(index)), _sz(int(count)), _p(p) if len(p) else None,
+                                               _sz(len(p)), _p(r)))
 
 
 def batch_range_proof_verify_bytes_host(blob, n, G, H, g, h, V=None, check=1, num_gpus=1):

@@ -25,6 +25,7 @@
 #include "ge25519_dev.h"
 #include "bp_prove_seed.h"
 #include "bp_codec.h"
+#include "bp_ids.h"
 
 static_assert(sizeof(fe25519) == 32, "fe25519 layout");
 static_assert(sizeof(ge25519) == 128, "ge25519 layout");
@@ -133,6 +134,7 @@ struct StreamWs {
     bp::PipPair pip;             // Pippenger MSM (hipbp_msm_pippenger*): both parts' buffers and its side stream
     Buf commit[bp::CB_COUNT];    // Pedersen commitments (hipbp_batch_pedersen_commit*): one chunk's terms
     Buf codec[bp::CDB_COUNT];    // proof blob encoder (hipbp_batch_proof_encode): the block counts
+    Buf ids[bp::IDB_COUNT];      // proof ids and Merkle roots (hipbp_merkle_root, hipbp_blob_proof_ids): levels, bad counts
     std::map<std::pair<int, int>, Pipeline*> pipes;   // one-shot verify pipelines, per (n, mode)
     hipError_t release(hipError_t first);
 };
@@ -575,6 +577,7 @@ hipError_t StreamWs::release(hipError_t first) {
     keep(accept_cnt.release());
     for (auto& b : commit) keep(b.release());
     for (auto& b : codec) keep(b.release());
+    for (auto& b : ids) keep(b.release());
     if (ipa_side) keep(hipStreamSynchronize(ipa_side));
     for (auto& half : ipa)
         for (auto& b : half) keep(b.release());
@@ -2996,6 +2999,173 @@ void cuda_benchmark_range_proof(int iterations, size_t bit_size) {
            "batched (hipbp_batch_range_proof_verify_host) %.1f verifies/s  passes %zu/%zu  verdicts agree %zu/%zu\n",
            n, count, dt1 / count * 1e3, count / dt2, pass, count, agree, count);
     fflush(stdout);
+}
+
+}  // extern "C"
+
+// ---- proof ids and the batch Merkle root (bp_ids.h, bp_ids.hip)
+namespace {
+
+// the stream's ids workspace grown for a root over `leaves` ids / a blob of `count` proofs
+int ids_workspace(Engine* e, hipStream_t s, size_t leaves, size_t count, bp::IdsWs& w) {
+    Buf(&ib)[bp::IDB_COUNT] = e->streams[s].ids;
+    size_t sz[bp::IDB_COUNT];
+    bp::ids_sizes(leaves, count, sz);
+    // (a grown buffer frees the old one: the stream's earlier call may still use it)
+    bool grow = false;
+    for (int k = 0; k < bp::IDB_COUNT; k++) grow = grow || (sz[k] > ib[k].cap && ib[k].p);
+    if (grow) BP_RET_ON(hipStreamSynchronize(s));
+    BP_RET_ON(need_all(ib, sz));
+    {
+        using namespace bp;
+        Buf(&b)[IDB_COUNT] = ib;
+        BP_IDS_BUFS(BP_BUF_FIELD)
+    }
+    return HIPBP_OK;
+}
+
+// fn(lo, hi) over [0, count) in contiguous parts on HIPBP_HOST_THREADS threads (unset: the machine's,
+// 16 at most; at least 256 items a thread, so a small batch stays on the caller's thread)
+template <class F>
+void host_parts(size_t count, F fn) {
+    const char* env = getenv("HIPBP_HOST_THREADS");
+    size_t nt = env && atoi(env) > 0 ? (size_t)atoi(env) : std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
+    nt = std::min(nt, (count + 255) / 256);
+    if (nt <= 1) {
+        fn((size_t)0, count);
+        return;
+    }
+    std::vector<std::thread> workers;
+    for (size_t k = 0; k < nt; k++) workers.emplace_back(fn, count * k / nt, count * (k + 1) / nt);
+    for (auto& w : workers) w.join();
+}
+
+}  // namespace
+
+extern "C" {
+
+int hipbp_batch_proof_ids(const hipbp_proof_batch* b, int with_blinding, uint8_t* ids_dev, uint8_t* kind_dev,
+                          void* stream) {
+    if (!b || (b->count && !ids_dev)) return codec_fail("proof_ids", "null argument");
+    if (const char* e = bp::codec_shape_error(b->count, b->n, b->ab_len, b->L_len, 0)) return codec_fail("proof_ids", e);
+    if (b->count && !((b->Vp || b->V) && b->A && b->S && b->T1 && b->T2 && b->t && b->a && b->b && b->c && b->x &&
+                      (!b->L_len || (b->L && b->R))))
+        return codec_fail("proof_ids", "null batch field");
+    if (with_blinding && b->count && (!b->taux || !b->mu)) return codec_fail("proof_ids", "with_blinding needs the batch's taux and mu");
+    if ((uintptr_t)ids_dev % 4) return codec_fail("proof_ids", "ids_dev must be 4-byte aligned");
+    if (b->count == 0) return HIPBP_OK;
+    const bp::CodecLayout l{b->count, b->ab_len, b->L_len, with_blinding ? 1 : 0};
+    BP_ENGINE_OR_RET(e);
+    (void)e;
+    bp::CodecArrays A;
+    const ge25519* pts[5] = {b->Vp ? b->Vp : b->V, b->A, b->S, b->T1, b->T2};
+    for (int k = 0; k < 5; k++) A.pt[k] = (bp::ge*)pts[k];
+    A.t = (bp::fe*)b->t; A.c = (bp::fe*)b->c; A.x = (bp::fe*)b->x; A.a = (bp::fe*)b->a; A.b = (bp::fe*)b->b;
+    A.taux = with_blinding ? (bp::fe*)b->taux : nullptr; A.mu = with_blinding ? (bp::fe*)b->mu : nullptr;
+    A.L = (bp::ge*)b->L; A.R = (bp::ge*)b->R;
+    bp::launch_proof_ids(A, l, b->n, ids_dev, kind_dev, pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_blob_proof_ids(const uint8_t* blob_dev, const hipbp_proof_blob_info* info, uint8_t* ids_dev, uint32_t* bad_dev,
+                         void* stream) {
+    if (!blob_dev || !info || !bad_dev || (info->count && !ids_dev)) return codec_fail("blob_proof_ids", "null argument");
+    if (const char* e = bp::codec_shape_error(info->count, info->n, info->ab_len, info->L_len, info->flags))
+        return codec_fail("blob_proof_ids", e);
+    const bp::CodecLayout l = bp::codec_layout(*info);
+    if (info->raw_count > info->count || l.bytes(info->raw_count) != info->bytes || (l.Sc() == 0 && info->raw_count != info->count))
+        return codec_fail("blob_proof_ids", "info does not describe a blob (use hipbp_proof_blob_header)");
+    if ((uintptr_t)blob_dev % 8) return codec_fail("blob_proof_ids", "blob_dev must be 8-byte aligned");
+    if ((uintptr_t)ids_dev % 4 || (uintptr_t)bad_dev % 4) return codec_fail("blob_proof_ids", "ids_dev and bad_dev must be 4-byte aligned");
+    BP_ENGINE_OR_RET(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    bp::IdsWs w;
+    if (int rc = ids_workspace(e, pick(stream), 0, info->count, w)) return rc;
+    bp::launch_blob_ids(bp::codec_view(blob_dev, info->bytes, l, info->raw_count), l, info->n, ids_dev, w, bad_dev, pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_merkle_root(const uint8_t* ids_dev, size_t count, uint8_t* root_dev, void* stream) {
+    if (!root_dev || (count && !ids_dev)) return codec_fail("merkle_root", "null argument");
+    if (count > bp::MERKLE_MAX_COUNT) return codec_fail("merkle_root", "count above 2^24");
+    if ((uintptr_t)ids_dev % 4 || (uintptr_t)root_dev % 4) return codec_fail("merkle_root", "ids_dev and root_dev must be 4-byte aligned");
+    BP_ENGINE_OR_RET(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    bp::IdsWs w;
+    if (int rc = ids_workspace(e, pick(stream), count, 0, w)) return rc;
+    bp::launch_merkle_root(ids_dev, count, root_dev, w, pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_proof_ids_host(const RangeProof* proofs, size_t count, size_t n, int with_blinding, uint8_t* ids) {
+    if (count && (!proofs || !ids)) return codec_fail("proof_ids_host", "null argument");
+    const size_t abl = count ? proofs[0].ip_proof.a.length : 1, Lr = count ? proofs[0].ip_proof.L_len : 0;
+    for (size_t i = 0; i < count; i++) {
+        const InnerProductProof& ip = proofs[i].ip_proof;
+        if (ip.a.length != abl || ip.b.length != abl || ip.L_len != Lr || ip.L.length < Lr || ip.R.length < Lr ||
+            !ip.a.elements || !ip.b.elements || (Lr && (!ip.L.elements || !ip.R.elements)))
+            return codec_fail("proof_ids_host", ("proof " + std::to_string(i) +
+                                                 ": another shape than the first proof's, or inconsistent vector lengths").c_str());
+    }
+    if (const char* e = bp::codec_shape_error(count, n, abl, Lr, 0)) return codec_fail("proof_ids_host", e);
+    const bp::CodecLayout l{count, abl, Lr, with_blinding ? 1 : 0};
+    host_parts(count, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) bp::ids_flat_proof(arrays_of_struct(proofs[i]), l, n, 0, ids + bp::ID_BYTES * i);
+    });
+    return HIPBP_OK;
+}
+
+int hipbp_blob_proof_ids_host(const uint8_t* blob, size_t bytes, uint8_t* ids) {
+    hipbp_proof_blob_info info;
+    if (const char* e = bp::codec_parse(blob, bytes, &info)) return codec_fail("blob_proof_ids_host", e);
+    if (info.count && !ids) return codec_fail("blob_proof_ids_host", "null ids");
+    const bp::CodecLayout l = bp::codec_layout(info);
+    const bp::BlobView v = bp::codec_view(blob, bytes, l, info.raw_count);
+    std::atomic<size_t> bad{0};
+    host_parts(info.count, [&](size_t lo, size_t hi) {
+        size_t b = 0;
+        for (size_t i = lo; i < hi; i++) b += bp::ids_blob_proof(v, l, info.n, i, ids + bp::ID_BYTES * i);
+        bad += b;
+    });
+    if (bad) {   // (not after a full parse)
+        memset(ids, 0, info.count * bp::ID_BYTES);
+        return codec_fail("blob_proof_ids_host", "a record failed its checks");
+    }
+    return HIPBP_OK;
+}
+
+int hipbp_merkle_root_host(const uint8_t* ids, size_t count, uint8_t root[32]) {
+    if (!root || (count && !ids)) return codec_fail("merkle_root_host", "null argument");
+    if (count > bp::MERKLE_MAX_COUNT) return codec_fail("merkle_root_host", "count above 2^24");
+    if (count == 0) {
+        uint32_t d[8];
+        bp::merkle_empty(d);
+        bp::ids_store(root, d);
+        return HIPBP_OK;
+    }
+    std::vector<std::vector<uint8_t>> lv;
+    bp::merkle_levels_cpu(ids, count, lv);
+    memcpy(root, lv.back().data(), bp::ID_BYTES);
+    return HIPBP_OK;
+}
+
+int hipbp_merkle_path_host(const uint8_t* ids, size_t count, size_t index, uint8_t* path, size_t* path_len) {
+    if (!ids || !path || !path_len) return codec_fail("merkle_path_host", "null argument");
+    if (count > bp::CODEC_MAX_COUNT) return codec_fail("merkle_path_host", "count above 2^22");
+    if (index >= count) return codec_fail("merkle_path_host", "index not below count");
+    std::vector<std::vector<uint8_t>> lv;
+    bp::merkle_levels_cpu(ids, count, lv);
+    *path_len = bp::merkle_path_cpu(lv, count, index, path);
+    return HIPBP_OK;
+}
+
+int hipbp_merkle_verify_host(const uint8_t id[32], size_t index, size_t count, const uint8_t* path, size_t path_len,
+                             const uint8_t root[32]) {
+    if (!id || !root || (path_len && !path)) return 0;
+    return bp::merkle_verify_cpu(id, index, count, path, path_len, root) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -256,6 +256,23 @@ inline void codec_sizes(size_t count, size_t (&sz)[CDB_COUNT]) {
     BP_CODEC_BUFS(BP_BUF_SIZE)
 }
 
+// Proof ids and Merkle roots (IdsWs, bp_ids.h).  A root over `leaves` ids goes level by level through
+// two buffers: level 1 (and 3, 5, ...: each smaller) in ping, level 2 (4, ...) in pong, 32 bytes a
+// node; the last level is written to the caller's root.  bad: one count of failed records per block
+// of 256 proofs of a blob of `count` proofs.
+inline size_t merkle_level_nodes(size_t leaves, int level) {
+    for (int k = 0; k < level; k++) leaves = (leaves + 1) >> 1;
+    return leaves;
+}
+#define BP_IDS_BUFS(X)                                            \
+    X(IDB_PING, ping, uint8_t, merkle_level_nodes(leaves, 1) * 32) \
+    X(IDB_PONG, pong, uint8_t, merkle_level_nodes(leaves, 2) * 32) \
+    X(IDB_BAD, bad, uint32_t, codec_blocks(count) * U32)
+enum IdsBuf { BP_IDS_BUFS(BP_BUF_ID) IDB_COUNT };
+inline void ids_sizes(size_t leaves, size_t count, size_t (&sz)[IDB_COUNT]) {
+    BP_IDS_BUFS(BP_BUF_SIZE)
+}
+
 // A verify slot (VerifyWs) for B proofs of n bits with Lb fold rounds; Lc = max(Lb, 1); m2 = B in mode 2
 // (range_proof_verify), whose buffers the other modes leave unallocated.  B_PERM, the lane orders,
 // is no VerifyWs field: the batch's sort sets size it.

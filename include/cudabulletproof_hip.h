@@ -571,6 +571,63 @@ int hipbp_batch_range_proof_verify_bytes_host(const uint8_t* blob, size_t bytes,
                                               const PointVector* G, const PointVector* H, const ge25519* g,
                                               const ge25519* h, int check, int num_gpus, uint8_t* ok);
 
+/* ---- Proof ids and a batch Merkle root: a name for a proof, a fingerprint for a batch,
+ * computed where the proofs are.  A proof's record is what an "HBPC" version 1 blob stores for it (above):
+ * its compact slot when the encoder classifies it compact (kind 0), else its raw record (kind 1), with
+ * the encoder's V (the batch's Vp when non-NULL, else V).  All integers little-endian:
+ *   hdr  = "hipbpProofIdV1" (14 bytes) | u8 kind | u8 f | u32 n | u32 ab_len | u32 L_len | u32 0      (32 bytes)
+ *   id   = SHA-256(hdr | record)
+ *   leaf = SHA-256(0x00 | id)      node = SHA-256(0x01 | left | right)
+ *   root(ids[0 .. count)) = RFC 6962 §2.1 MTH with the ids as the leaf inputs; count = 0: SHA-256("")
+ * kind and f are hashed: a proof has one id without its blinding scalars (f = 0) and another with
+ * them.  The tree is built level by level: nodes (2k, 2k + 1) are paired, an unpaired last node moves
+ * up unchanged (the same tree as the RFC's recursive split).  The audit path of leaf `index` is RFC
+ * 6962 §2.1.1 PATH, bottom-up: at each level no entry if the node is the level's unpaired last one,
+ * else its sibling; at most 22 entries for count <= 2^22.  The ids of a batch, of its blob, on the
+ * GPU and on the CPU are the same bytes.
+ *
+ * The ids of a device batch: ids_dev (DEVICE, 4-byte aligned, [count * 32]) and, when kind_dev is not
+ * NULL, each proof's kind (DEVICE, [count]).  One launch, one lane per proof: classify, then hash
+ * the record from the flat arrays.  The encoder's limits and checks: a bad shape, with_blinding
+ * without taux and mu, or a null pointer give HIPBP_ERR_ARG, write nothing and enqueue nothing.
+ * count = 0 is a no-op.  Asynchronous on `stream`. */
+int hipbp_batch_proof_ids(const hipbp_proof_batch* batch, int with_blinding, uint8_t* ids_dev, uint8_t* kind_dev,
+                          void* stream);
+/* The ids of the proofs of a DEVICE blob (8-byte aligned) whose header the host validated into *info
+ * (hipbp_proof_blob_header), as hipbp_batch_proof_decode takes it.  One lane per proof: its kind byte,
+ * then its compact slot or the raw record raw_index names for it (binary search).  Every index read
+ * from the blob is checked against the header and info->bytes before use, by the decoder's rules; a
+ * record that fails gets an all-zero id and is counted: *bad_dev (DEVICE, 4-byte aligned, set by the
+ * call) = the number that failed, 0 for a blob hipbp_proof_blob_parse accepts.  The per-block counts
+ * live in a workspace kept per (device, stream), freed by hipbp_release_stream_workspaces.
+ * HIPBP_ERR_ARG enqueues nothing.  Asynchronous on `stream`. */
+int hipbp_blob_proof_ids(const uint8_t* blob_dev, const hipbp_proof_blob_info* info, uint8_t* ids_dev, uint32_t* bad_dev,
+                         void* stream);
+/* root_dev (DEVICE, 4-byte aligned, [32]) = the Merkle root over ids_dev (DEVICE, 4-byte aligned,
+ * [count * 32]); count <= 2^24, count = 0 gives SHA-256("").  One launch per level, one lane per node
+ * of the level above (level 0 fused with the leaf hash); the levels alternate between two buffers of
+ * a workspace kept per (device, stream), grow-only, freed by hipbp_release_stream_workspaces.  A
+ * multi-GPU caller concatenates its shards' ids.  HIPBP_ERR_ARG enqueues nothing.  Asynchronous on
+ * `stream`. */
+int hipbp_merkle_root(const uint8_t* ids_dev, size_t count, uint8_t* root_dev, void* stream);
+/* The same ids from the reference's host structs, on the CPU: no HIP call, no device needed.
+ * hipbp_proofs_encode_host's checks: the first proof sets ab_len and L_len; a proof of another shape,
+ * or with inconsistent vector lengths, gives HIPBP_ERR_ARG naming its index, nothing written.  ids
+ * (HOST, [count * 32]).  count = 0 is a no-op.  The proofs are split over HIPBP_HOST_THREADS threads
+ * (unset: the machine's, 16 at most; at least 256 proofs a thread), as are hipbp_blob_proof_ids_host's. */
+int hipbp_proof_ids_host(const RangeProof* proofs, size_t count, size_t n, int with_blinding, uint8_t* ids);
+/* ... and from a HOST blob, which is parsed fully first (hipbp_proof_blob_parse): a malformed blob
+ * gives HIPBP_ERR_ARG with the parser's message, nothing written.  ids (HOST, [count * 32]). */
+int hipbp_blob_proof_ids_host(const uint8_t* blob, size_t bytes, uint8_t* ids);
+/* The root, an audit path and its check, on the CPU.  _path_host: path (HOST, room for 22 entries of
+ * 32 bytes) and *path_len for leaf `index` < count <= 2^22.  _verify_host recomputes the root from
+ * (id, index, count, path) and returns 1 only if it consumes exactly path_len entries and arrives at
+ * `root`; 0 otherwise, also for index >= count or a null pointer. */
+int hipbp_merkle_root_host(const uint8_t* ids, size_t count, uint8_t root[32]);
+int hipbp_merkle_path_host(const uint8_t* ids, size_t count, size_t index, uint8_t* path, size_t* path_len);
+int hipbp_merkle_verify_host(const uint8_t id[32], size_t index, size_t count, const uint8_t* path, size_t path_len,
+                             const uint8_t root[32]);
+
 /* Canonical-tree MSM on device buffers.  Asynchronous on `stream`; the MSM, MSM-batch
  * and point-tree calls keep one workspace per (device, stream), so calls on different streams may
  * run concurrently. */
@@ -658,7 +715,7 @@ int hipbp_sm_probe(int force, ge25519* out, const fe25519* scalars, const ge2551
 int hipbp_sm_form_probe(int form, int force, ge25519* out, const fe25519* scalars, const ge25519* points, size_t count,
                         void* stream);
 /* Frees every workspace the library caches for `stream` on the current device (canonical MSM /
- * point-tree, prover, the Pedersen commitments' terms, the seeded prover's scalars and keys, the accepted prover's retry workspace, the proof blob encoder's block counts, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
+ * point-tree, prover, the Pedersen commitments' terms, the seeded prover's scalars and keys, the accepted prover's retry workspace, the proof blob encoder's block counts, the proof ids' and Merkle root's level buffers and bad counts, one-shot verify pipelines, the Pippenger workspace pair and the IPA prover's
  * workspace pair, each with its side stream and events), after waiting for the stream.  Workspaces otherwise live as long as the process;
  * a caller that makes short-lived streams calls this before destroying one.  No reference
  * counterpart. */
