@@ -648,6 +648,39 @@ struct HostProofStage {
     std::vector<ge25519> L, R;
 };
 
+// ---- the host-data entry points' shards on their devices (the contract: bp_host_prove.h, DESIGN
+// §15).  open() reads num_gpus and HIPBP_HOST_SHARDS for a call of `count` items and notes the
+// caller's device; run() cuts M items into the shards' blocks and calls shard(device, block, stop)
+// for each, shard d for device (dev0 + d) % ndev, so num_gpus = 1 stays on the caller's (one rank per
+// GPU in a process group).  A shard leaves its message in g_err; the first failure is reported as
+// "device d: ..." and the caller's device is restored.
+struct HostFan {
+    int ndev = 0, dev0 = 0, ng = 0;
+    int open(size_t count, int num_gpus) {
+        BP_RET_ON(hipGetDeviceCount(&ndev));
+        if (int rc = bp::resolve_host_shards(num_gpus, ndev, getenv("HIPBP_HOST_SHARDS"), count, &ng, &g_err)) return rc;
+        BP_RET_ON(hipGetDevice(&dev0));
+        return HIPBP_OK;
+    }
+    template <class F>
+    int run(size_t M, F shard) {
+        const std::vector<bp::HostShard> shards = bp::plan_host_shards(M, ng);
+        const bp::HostFanFailure f =
+            bp::host_fanout(shards, [&](const bp::HostShard& sh, const bp::HostStop& stop, std::string& err) {
+                const int rc = shard((dev0 + sh.d) % ndev, sh, stop);
+                if (rc != HIPBP_OK) err = g_err;
+                return rc;
+            });
+        if (f.k != shards.size()) {
+            g_err = "device " + std::to_string(shards[f.k].d) + ": " + f.err;
+            (void)hipSetDevice(dev0);
+            return f.rc;
+        }
+        BP_RET_ON(hipSetDevice(dev0));
+        return HIPBP_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1166,6 +1199,11 @@ struct AcceptStats {
     int rounds = 0;
     uint32_t m[16] = {};
     float ms[AK_COUNT] = {};
+    void add(const AcceptStats& s) {   // another call's, of other proofs: the rounds of the longer one
+        rounds = std::max(rounds, s.rounds);
+        for (int r = 0; r < 16; r++) m[r] += s.m[r];
+        for (int q = 0; q < AK_COUNT; q++) ms[q] += s.ms[q];
+    }
 };
 static thread_local AcceptStats g_accept_stats;
 
@@ -1331,7 +1369,6 @@ struct HostProveCall {
     int max_attempts, check;      // the accepted prover's (max_attempts = 0: the seeded prover)
     size_t piece;                 // ... and the proofs per piece of a chunk's way back to the host
     bp::ProofOwner* own;
-    std::atomic<bool>* failed;    // set by the first shard that fails: the others stop at their next chunk
 };
 
 // A shard's hold on its device's prove-host staging: the engine's two streams, the pinned and the
@@ -1392,7 +1429,8 @@ struct HostStage {
 // before the slot's next chunk is staged, so one chunk's copies and unpacking run under the other's
 // kernels.  Slot layout (pinned host and device alike):
 // v | gamma [c] | V A S T1 T2 [c] | taux mu t c x a b [c] | L R [c Lr] | valid [c].
-static int prove_host_seeded_shard(int dev, const HostProveCall& c, const std::vector<bp::HostChunk>& chunks) {
+static int prove_host_seeded_shard(int dev, const HostProveCall& c, const std::vector<bp::HostChunk>& chunks,
+                                   const bp::HostStop& stop) {
     const size_t n = c.n, FE = bp::FE, Lr = (size_t)log2i(n), nch = chunks.size();
     const size_t CH = chunks[0].c;   // (the plan's chunks are all of this size but for a shorter last one)
     // a slot: v | gamma [CH], then the proof-output layout (bp::OutLayout)
@@ -1421,9 +1459,8 @@ static int prove_host_seeded_shard(int dev, const HostProveCall& c, const std::v
             if (rc != HIPBP_OK) break;
         }
         if (ch >= nch) continue;
-        if (c.failed->load()) {
-            rc = HIPBP_ERR_DEVICE;
-            what = "stopped: another shard failed";
+        if (stop.raised()) {   // another shard failed: no further chunk
+            rc = bp::HOST_SHARD_STOPPED;
             break;
         }
         const size_t c0 = chunks[ch].c0, cc = chunks[ch].c;
@@ -1451,7 +1488,6 @@ static int prove_host_seeded_shard(int dev, const HostProveCall& c, const std::v
     }
     if (rc != HIPBP_OK) {
         sg.drain();
-        c.failed->store(true);
         g_err = what;
     }
     return rc;
@@ -1466,7 +1502,7 @@ static int prove_host_seeded_shard(int dev, const HostProveCall& c, const std::v
 // after another: a chunk's last piece is unpacked before the next chunk's device call begins.
 // `total`: the device calls' statistics, summed over the chunks.
 static int prove_host_accepted_shard(int dev, const HostProveCall& c, const std::vector<bp::HostChunk>& chunks,
-                                     AcceptStats* total) {
+                                     const bp::HostStop& stop, AcceptStats* total) {
     const size_t n = c.n, FE = bp::FE, GE = bp::GE, Lr = (size_t)log2i(n);
     const size_t C = chunks[0].c, P = std::min(c.piece, C);
     const auto up = [](size_t b) { return (b + 127) & ~(size_t)127; };
@@ -1484,9 +1520,8 @@ static int prove_host_accepted_shard(int dev, const HostProveCall& c, const std:
     uint8_t* ds = sg.dbuf;
     uint8_t* datt = sg.dbuf + d_att;
     for (size_t ch = 0; ch < chunks.size() && rc == HIPBP_OK; ch++) {
-        if (c.failed->load()) {
-            rc = HIPBP_ERR_DEVICE;
-            what = "stopped: another shard failed";
+        if (stop.raised()) {   // another shard failed: no further chunk
+            rc = bp::HOST_SHARD_STOPPED;
             break;
         }
         const size_t c0 = chunks[ch].c0, cc = chunks[ch].c;
@@ -1514,9 +1549,7 @@ static int prove_host_accepted_shard(int dev, const HostProveCall& c, const std:
                             dG + 2 * n + 1, nullptr, 0, &out, datt, sg.st[0]);
         if (rc != HIPBP_OK) { what = g_err; break; }
         // (the call returned with stream 0 drained: the chunk is complete, the pinned slots are free)
-        total->rounds = std::max(total->rounds, g_accept_stats.rounds);
-        for (int r = 0; r < 16; r++) total->m[r] += g_accept_stats.m[r];
-        for (int q = 0; q < AK_COUNT; q++) total->ms[q] += g_accept_stats.ms[q];
+        total->add(g_accept_stats);
         const size_t np = (cc + P - 1) / P;
         for (size_t j = 0; j < np + 2 && rc == HIPBP_OK; j++) {
             const int k = (int)(j & 1);
@@ -1558,7 +1591,6 @@ static int prove_host_accepted_shard(int dev, const HostProveCall& c, const std:
     }
     if (rc != HIPBP_OK) {
         sg.drain();
-        c.failed->store(true);
         g_err = what;
     }
     return rc;
@@ -1569,6 +1601,10 @@ static size_t env_chunk(const char* name, size_t dflt) {   // a chunk size: at m
     if (const char* ce = getenv(name))
         if (atol(ce) > 0) ch = (size_t)atol(ce);
     return std::min(ch, (size_t)1 << 22);
+}
+static size_t env_commit_chunk(size_t count) {   // HIPBP_COMMIT_CHUNK for a call of `count` (bp::commit_chunk's rule)
+    const char* ce = getenv("HIPBP_COMMIT_CHUNK");
+    return bp::commit_chunk(count, ce ? atoll(ce) : 0);
 }
 
 // Both host provers: the argument checks (nothing written on an error), the shards' threads, the
@@ -1590,73 +1626,30 @@ static int prove_host_run(RangeProof* proofs, uint8_t* valid, uint8_t* attempts,
         if (check != 1 && check != 2) { g_err = "accepted prover: check must be 1 or 2"; return HIPBP_ERR_ARG; }
         if (!attempts) { g_err = "accepted prover: null attempts"; return HIPBP_ERR_ARG; }
     }
-    int ndev = 0;
-    BP_RET_ON(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) { g_err = "no HIP device"; return HIPBP_ERR_DEVICE; }
-    if (num_gpus > ndev) {   // hipbp_batch_range_proof_verify_host's rule and message
-        g_err = "num_gpus = " + std::to_string(num_gpus) + " but " + std::to_string(ndev) + " HIP device(s) visible";
-        return HIPBP_ERR_ARG;
-    }
-    int ng = num_gpus <= 0 ? ndev : num_gpus;
-    // HIPBP_HOST_SHARDS=k, as the verifier reads it (only when the caller leaves num_gpus <= 0): k
-    // shards (at most 64 and at most one per proof), shard d on device (current + d) % ndev, so the
-    // split, its threads and the merge also run on a one-GPU box; shards that share a device run
-    // one after another (prove_host_mu)
-    if (num_gpus <= 0)
-        if (const char* hs = getenv("HIPBP_HOST_SHARDS"))
-            if (atoi(hs) > 0) ng = (int)std::min<size_t>(std::min(atoi(hs), 64), count);
-    int dev0 = 0;   // shard d runs on device (dev0 + d) % ndev: num_gpus = 1 stays on the caller's
-    BP_RET_ON(hipGetDevice(&dev0));
+    HostFan fan;
+    if ((rc = fan.open(count, num_gpus)) != HIPBP_OK) return rc;
     const size_t chunk = accepted ? env_chunk("HIPBP_PROVE_HOST_ACCEPT_CHUNK", 65536) : env_chunk("HIPBP_PROVE_HOST_CHUNK", 16384);
     if (accepted) g_accept_stats = AcceptStats{};
 
     bp::ProofOwner own(proofs, valid, attempts, count);   // (zeroes the three outputs)
-    std::atomic<bool> failed(false);
     const HostProveCall call{v, gamma, n, G, H, g, h, seed32, accepted ? max_attempts : 0, check,
-                             env_chunk("HIPBP_PROVE_HOST_CHUNK", 16384), &own, &failed};
-    const std::vector<bp::HostShard> shards = bp::plan_host_shards(count, ng);
-    const size_t ns = shards.size();
-    std::vector<int> rcs(ns, HIPBP_OK);
-    std::vector<std::string> errs(ns);
-    std::vector<AcceptStats> stats(ns);
-    auto run_shard = [&](size_t k) {
-        const bp::HostShard& sh = shards[k];
+                             env_chunk("HIPBP_PROVE_HOST_CHUNK", 16384), &own};
+    std::vector<AcceptStats> stats(fan.ng);   // [shard d]: its device calls', carried back from its thread
+    // A call of one shard has the caller's thread for it: the proofs' vectors then come from the
+    // caller's malloc arena as they always did; from a thread of its own the one-device seeded call
+    // measured 190.7 ms against the parent commit's 180.4 (174.3-184.8), DESIGN §15.
+    rc = fan.run(count, [&](int dev, const bp::HostShard& sh, const bp::HostStop& stop) {
         const std::vector<bp::HostChunk> chunks = bp::plan_host_chunks(sh, std::min(chunk, sh.hi - sh.lo), index_base);
-        const int dev = (dev0 + sh.d) % ndev;
-        rcs[k] = accepted ? prove_host_accepted_shard(dev, call, chunks, &stats[k])
-                          : prove_host_seeded_shard(dev, call, chunks);
-        if (rcs[k] != HIPBP_OK) errs[k] = g_err;   // g_err is per thread
-    };
-    // One host thread per shard.  A call of one shard has the caller's thread for it (shard 0 is on
-    // the caller's device): the proofs' vectors then come from the caller's malloc arena as they
-    // always did; from a thread of its own the one-device seeded call measured 190.7 ms against the
-    // parent commit's 180.4 (174.3-184.8), DESIGN §15.
-    if (ns == 1 && shards[0].d == 0) {
-        run_shard(0);
-    } else {
-        std::vector<std::thread> workers;
-        for (size_t k = 0; k < ns; k++) workers.emplace_back(run_shard, k);
-        for (auto& w : workers) w.join();
-    }
-    // the first failure in shard order that is a shard's own (not a stop after another's)
-    size_t bad = ns;
-    for (size_t k = 0; k < ns; k++)
-        if (rcs[k] != HIPBP_OK && (bad == ns || errs[bad].rfind("stopped:", 0) == 0)) bad = k;
-    if (bad != ns) {
+        return accepted ? prove_host_accepted_shard(dev, call, chunks, stop, &stats[sh.d])
+                        : prove_host_seeded_shard(dev, call, chunks, stop);
+    });
+    if (rc != HIPBP_OK) {
         own.rollback();   // every vector of every shard freed, proofs, valid and attempts zero
-        g_err = "device " + std::to_string(shards[bad].d) + ": " + errs[bad];
-        (void)hipSetDevice(dev0);
-        return rcs[bad];
+        return rc;
     }
-    BP_RET_ON(hipSetDevice(dev0));
-    if (accepted) {   // the device calls' statistics, carried back from the shards' threads
-        AcceptStats& t = g_accept_stats;
-        t = AcceptStats{};   // (a shard run on this thread left its last chunk's here)
-        for (const AcceptStats& s : stats) {
-            t.rounds = std::max(t.rounds, s.rounds);
-            for (int r = 0; r < 16; r++) t.m[r] += s.m[r];
-            for (int q = 0; q < AK_COUNT; q++) t.ms[q] += s.ms[q];
-        }
+    if (accepted) {
+        g_accept_stats = AcceptStats{};   // (a shard run on this thread left its last chunk's here)
+        for (const AcceptStats& st : stats) g_accept_stats.add(st);
     }
     return HIPBP_OK;
 }
@@ -1695,8 +1688,7 @@ static int commit_run(Engine& e, ge25519* out, uint8_t* ok, const ge25519* V, co
                       size_t count, const bp::ge* g, const bp::ge* h, const bp::ge* ptab, int pbits, size_t gens_n,
                       hipStream_t s) {
     using namespace bp;   // the table's ids and types
-    const char* ce = getenv("HIPBP_COMMIT_CHUNK");
-    const size_t chunk = commit_chunk(count, ce ? atoll(ce) : 0);
+    const size_t chunk = env_commit_chunk(count);
     std::lock_guard<std::mutex> lk(e.mu);
     Buf(&b)[CB_COUNT] = e.streams[s].commit;
     size_t sz[CB_COUNT];
@@ -1764,8 +1756,7 @@ static int commit_host_shard(int dev, ge25519* out, const fe25519* v, const fe25
     BP_ENGINE_OR_RET(e);
     std::unique_lock<std::mutex> hold(e->prove_host_mu);
     const size_t FE = bp::FE, GE = bp::GE;
-    const char* ce = getenv("HIPBP_COMMIT_CHUNK");
-    const size_t piece = bp::commit_chunk(hi - lo, ce ? atoll(ce) : 0);
+    const size_t piece = env_commit_chunk(hi - lo);
     hipStream_t s = e->stream;
     BP_RET_ON(hipStreamSynchronize(s));   // (the staging may grow)
     BP_RET_ON(e->prove_host_dev.need(2 * GE + piece * (2 * FE + GE)));
@@ -1790,43 +1781,11 @@ int hipbp_batch_pedersen_commit_host(ge25519* out, const fe25519* v, const fe255
                                      const ge25519* g, const ge25519* h, int num_gpus) {
     if (count == 0) return HIPBP_OK;
     if (!out || !v || !gamma || !g || !h) { g_err = "null argument"; return HIPBP_ERR_ARG; }
-    int ndev = 0;
-    BP_RET_ON(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) { g_err = "no HIP device"; return HIPBP_ERR_DEVICE; }
-    if (num_gpus > ndev) {   // hipbp_batch_range_proof_verify_host's rule and message
-        g_err = "num_gpus = " + std::to_string(num_gpus) + " but " + std::to_string(ndev) + " HIP device(s) visible";
-        return HIPBP_ERR_ARG;
-    }
-    int ng = num_gpus <= 0 ? ndev : num_gpus;
-    if (num_gpus <= 0)   // HIPBP_HOST_SHARDS=k, as the host provers read it
-        if (const char* hs = getenv("HIPBP_HOST_SHARDS"))
-            if (atoi(hs) > 0) ng = (int)std::min<size_t>(std::min(atoi(hs), 64), count);
-    int dev0 = 0;   // shard d runs on device (dev0 + d) % ndev: num_gpus = 1 stays on the caller's
-    BP_RET_ON(hipGetDevice(&dev0));
-    const std::vector<bp::HostShard> shards = bp::plan_host_shards(count, ng);   // the host provers' split
-    const size_t ns = shards.size();
-    std::vector<int> rcs(ns, HIPBP_OK);
-    std::vector<std::string> errs(ns);
-    auto run_shard = [&](size_t k) {
-        const bp::HostShard& sh = shards[k];
-        rcs[k] = commit_host_shard((dev0 + sh.d) % ndev, out, v, gamma, sh.lo, sh.hi, g, h);
-        if (rcs[k] != HIPBP_OK) errs[k] = g_err;   // g_err is per thread
-    };
-    if (ns == 1 && shards[0].d == 0) {
-        run_shard(0);
-    } else {
-        std::vector<std::thread> workers;
-        for (size_t k = 0; k < ns; k++) workers.emplace_back(run_shard, k);
-        for (auto& w : workers) w.join();
-    }
-    for (size_t k = 0; k < ns; k++)   // the first failure in shard order, every thread joined
-        if (rcs[k] != HIPBP_OK) {
-            g_err = "device " + std::to_string(shards[k].d) + ": " + errs[k];
-            (void)hipSetDevice(dev0);
-            return rcs[k];
-        }
-    BP_RET_ON(hipSetDevice(dev0));
-    return HIPBP_OK;
+    HostFan fan;
+    if (int rc = fan.open(count, num_gpus)) return rc;
+    return fan.run(count, [&](int dev, const bp::HostShard& sh, const bp::HostStop&) {
+        return commit_host_shard(dev, out, v, gamma, sh.lo, sh.hi, g, h);
+    });
 }
 
 // ---- stand-alone IPA prover (bp_ipa_prove.hip).  The engine's lock is held by the caller.
@@ -2508,52 +2467,6 @@ int host_shard(int dev, const Src& src, size_t B, size_t n, const PointVector* G
     return rc;
 }
 
-// How the host verifiers read num_gpus: the devices visible (*ndev), the caller's current device
-// (*dev0: shard d runs on device (dev0 + d) % ndev, so num_gpus = 1 stays on it, one rank per GPU in
-// a process group) and the shards (*ng).  HIPBP_HOST_SHARDS=k (tests, only when the caller leaves
-// num_gpus <= 0): k shards (at most 64 and at most one per proof), so the multi-device split, its host
-// threads and the verdict merge also run on a one-GPU box (threads of one device serialise on its
-// engine's mutex).
-int host_verify_devices(size_t count, int num_gpus, int* ng, int* ndev, int* dev0) {
-    BP_RET_ON(hipGetDeviceCount(ndev));
-    if (*ndev <= 0) { g_err = "no HIP device"; return HIPBP_ERR_DEVICE; }
-    if (num_gpus > *ndev) {   // asked for more devices than are visible: an error, not a silent fallback
-        g_err = "num_gpus = " + std::to_string(num_gpus) + " but " + std::to_string(*ndev) + " HIP device(s) visible";
-        return HIPBP_ERR_ARG;
-    }
-    *ng = num_gpus <= 0 ? *ndev : num_gpus;
-    if (num_gpus <= 0)
-        if (const char* hs = getenv("HIPBP_HOST_SHARDS"))
-            if (atoi(hs) > 0) *ng = (int)std::min<size_t>(std::min(atoi(hs), 64), std::max<size_t>(count, 1));
-    BP_RET_ON(hipGetDevice(dev0));
-    return HIPBP_OK;
-}
-// M proofs in contiguous blocks over ng shards, one host thread each: shard(device, lo, hi).  The
-// first failure is reported as "device d: ..." after every thread was joined; the caller's device
-// is restored.
-template <class F>
-int host_verify_fanout(int ng, int ndev, int dev0, size_t M, F shard) {
-    std::vector<int> rcs(ng, HIPBP_OK);
-    std::vector<std::string> errs(ng);
-    std::vector<std::thread> workers;
-    for (int d = 0; d < ng; d++) {
-        const size_t lo = M * d / ng, hi = M * (d + 1) / ng;
-        if (hi == lo) continue;
-        workers.emplace_back([&, d, lo, hi]() {
-            rcs[d] = shard((dev0 + d) % ndev, lo, hi);
-            if (rcs[d] != HIPBP_OK) errs[d] = g_err;   // g_err is per thread
-        });
-    }
-    for (auto& w : workers) w.join();
-    for (int d = 0; d < ng; d++)
-        if (rcs[d] != HIPBP_OK) {
-            g_err = "device " + std::to_string(d) + ": " + errs[d];
-            (void)hipSetDevice(dev0);
-            return rcs[d];
-        }
-    BP_RET_ON(hipSetDevice(dev0));
-    return HIPBP_OK;
-}
 // the shape checks of the device batch (n a power of two, L_len <= log2 n) for a host batch
 int host_verify_shape(size_t n, size_t abl, size_t Lr) {
     hipbp_proof_batch probe;
@@ -2579,8 +2492,8 @@ int hipbp_batch_range_proof_verify_host(const RangeProof* proofs, const ge25519*
         g_err = "null argument";
         return HIPBP_ERR_ARG;
     }
-    int ng = 0, ndev = 0, dev0 = 0;
-    int rc = host_verify_devices(count, num_gpus, &ng, &ndev, &dev0);
+    HostFan fan;
+    int rc = fan.open(count, num_gpus);
     if (rc != HIPBP_OK) return rc;
     // The flat batch needs one (a/b length, rounds) shape: the first proof that passes the checks
     // sets it (the reference prover's proofs all share it); proofs of another shape go one by one.
@@ -2601,8 +2514,9 @@ int hipbp_batch_range_proof_verify_host(const RangeProof* proofs, const ge25519*
         (ip.a.length == abl && ip.L_len == Lr ? main : other).push_back(i);
     }
     if (!main.empty() && (rc = host_verify_shape(n, abl, Lr)) != HIPBP_OK) return rc;
-    rc = host_verify_fanout(ng, ndev, dev0, main.size(), [&](int dev, size_t lo, size_t hi) {
-        return host_shard(dev, StructChunks{proofs, V, main.data() + lo, abl, Lr, n}, hi - lo, n, G, H, nullptr, h, 1, ok);
+    // (the shards: as many as `count` asks for, cut from the index list)
+    rc = fan.run(main.size(), [&](int dev, const bp::HostShard& sh, const bp::HostStop&) {
+        return host_shard(dev, StructChunks{proofs, V, main.data() + sh.lo, abl, Lr, n}, sh.hi - sh.lo, n, G, H, nullptr, h, 1, ok);
     });
     if (rc != HIPBP_OK) return rc;
     for (size_t i : other)
@@ -2805,11 +2719,11 @@ int hipbp_batch_range_proof_verify_bytes_host(const uint8_t* blob, size_t bytes,
     if (info.count == 0) return HIPBP_OK;
     int rc = host_verify_shape(n, info.ab_len, info.L_len);
     if (rc != HIPBP_OK) return rc;
-    int ng = 0, ndev = 0, dev0 = 0;
-    if ((rc = host_verify_devices(info.count, num_gpus, &ng, &ndev, &dev0)) != HIPBP_OK) return rc;
+    HostFan fan;
+    if ((rc = fan.open(info.count, num_gpus)) != HIPBP_OK) return rc;
     const bp::CodecLayout l = bp::codec_layout(info);
-    return host_verify_fanout(ng, ndev, dev0, info.count, [&](int dev, size_t lo, size_t hi) {
-        return host_shard(dev, BlobChunks{blob, l, info.raw_count, n, lo, V}, hi - lo, n, G, H, g, h, check, ok);
+    return fan.run(info.count, [&](int dev, const bp::HostShard& sh, const bp::HostStop&) {
+        return host_shard(dev, BlobChunks{blob, l, info.raw_count, n, sh.lo, V}, sh.hi - sh.lo, n, G, H, g, h, check, ok);
     });
 }
 

@@ -1,12 +1,18 @@
-// bp_host_prove.h — the host provers' plan and result owner (internal to the library): the two parts
-// of hipbp_batch_generate_range_proof_host_sharded / _accepted_host that no GPU run exercises, the
-// split of a call into shards and chunks and the rollback after a failure.  Host-only and pure: no
-// HIP runtime calls, so tests/host_prove_check.hip runs both on a CPU.
+// bp_host_prove.h — the host-data entry points' shard contract and the host provers' plan and result
+// owner (internal to the library): the parts of the host verifiers, provers and commitments that no
+// GPU run exercises, the shard count, the split of a call into shards and chunks, the shards' threads
+// with the merge of their results, and the rollback after a failure.  Host-only and pure: no HIP
+// runtime calls, so tests/host_prove_check.hip runs them all on a CPU.
 #pragma once
+#include <algorithm>
+#include <atomic>
+#include <climits>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "bp_layout.h"
@@ -28,6 +34,67 @@ inline std::vector<HostShard> plan_host_shards(size_t count, int ng) {
         if (hi > lo) out.push_back(HostShard{d, lo, hi});
     }
     return out;
+}
+
+// How every host-data entry point reads num_gpus (count >= 1 proofs, ndev devices visible, env =
+// HIPBP_HOST_SHARDS's value or null): num_gpus >= 1 asks for that many shards and is an error beyond
+// ndev; num_gpus <= 0 takes every visible device, or env's k >= 1 shards, at most 64 and one per
+// proof (more shards than devices share them in turn: the split also runs on a one-GPU box).
+inline int resolve_host_shards(int num_gpus, int ndev, const char* env, size_t count, int* ng, std::string* err) {
+    if (ndev <= 0) { *err = "no HIP device"; return HIPBP_ERR_DEVICE; }
+    if (num_gpus > ndev) {   // asked for more devices than are visible: an error, not a silent fallback
+        *err = "num_gpus = " + std::to_string(num_gpus) + " but " + std::to_string(ndev) + " HIP device(s) visible";
+        return HIPBP_ERR_ARG;
+    }
+    *ng = num_gpus <= 0 ? ndev : num_gpus;
+    if (num_gpus <= 0 && env && atoi(env) > 0) *ng = (int)std::min<size_t>(std::min(atoi(env), 64), count);
+    return HIPBP_OK;
+}
+
+// ------------------------------------------------------------------ the fan-out
+// The flag a fan-out's shards share: raised once a shard has failed on its own, polled by the
+// others between chunks; a shard that gives up for it returns HOST_SHARD_STOPPED.
+class HostStop {
+    std::atomic<bool> up_{false};
+
+  public:
+    bool raised() const { return up_.load(); }
+    void raise() { up_.store(true); }
+};
+constexpr int HOST_SHARD_STOPPED = INT_MIN;   // (no return code of the library's)
+
+// run(shard, stop, err) -> return code, once per shard, each on a thread of its own; a call of one
+// shard with d = 0 (the caller's device) has the caller's thread for it.  `err` is the shard's own
+// message slot (the library's last-error string is per thread).  Every thread is joined before any
+// result is read.  Returns the first failure in shard order that is a shard's own, not a stop after
+// another's (one exists whenever any shard stopped: only such a failure raises the flag); k ==
+// shards.size(): none.
+struct HostFanFailure {
+    size_t k;
+    int rc;
+    std::string err;
+};
+template <class Run>
+HostFanFailure host_fanout(const std::vector<HostShard>& shards, Run run) {
+    const size_t ns = shards.size();
+    HostStop stop;
+    std::vector<int> rcs(ns, HIPBP_OK);
+    std::vector<std::string> errs(ns);
+    auto own_failure = [&](size_t k) { return rcs[k] != HIPBP_OK && rcs[k] != HOST_SHARD_STOPPED; };
+    auto one = [&](size_t k) {
+        rcs[k] = run(shards[k], (const HostStop&)stop, errs[k]);
+        if (own_failure(k)) stop.raise();
+    };
+    if (ns == 1 && shards[0].d == 0) {
+        one(0);
+    } else {
+        std::vector<std::thread> workers;
+        for (size_t k = 0; k < ns; k++) workers.emplace_back(one, k);
+        for (auto& w : workers) w.join();
+    }
+    for (size_t k = 0; k < ns; k++)
+        if (own_failure(k)) return HostFanFailure{k, rcs[k], errs[k]};
+    return HostFanFailure{ns, HIPBP_OK, std::string()};
 }
 
 // A shard's chunks, in order: proofs [c0, c0 + c) of the call, c = chunk but for a shorter last one,

@@ -6,11 +6,19 @@
 //           differ in size by at most one, none empty when ng <= count; every shard's chunks cover it
 //           in order and carry index_base + c0 mod 2^64 (restated here with 128-bit arithmetic); the
 //           wrap past 2^64 is reached
+//   count:  the shard count over num_gpus x ndev x HIPBP_HOST_SHARDS's value x count against its rule
+//           restated here: the two errors with their codes and messages, the override only at
+//           num_gpus <= 0, capped at 64 and at one shard per proof
+//   fanout: host lambdas as shards: every callback once and returned before the fan-out returns, the
+//           caller's thread only for a single shard with d = 0; shard k failing is the one reported,
+//           with its own message; of two own failures among shards stopped for the flag, the first
+//           in shard order, whichever came first in time
 //   owner:  9 proofs (L_len 0 and 4, one refused value, with and without attempts) filled from three
 //           threads through a counting allocator, then rolled back: no vector left, every output byte
 //           zero; the same with the k-th allocation failing, for every k up to the total
 // Prints "<checks> <failures>"; exit status 1 on any failure.
 #include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -85,6 +93,119 @@ static void plan() {
                 }
     CHECK(wraps > 0, "the wrap past 2^64 was never reached");
     CHECK(multi_chunk > 0 && short_last > 0, "the grid has no shard of several chunks / no short last chunk");
+}
+
+// ------------------------------------------------------------------ shard count
+static void shard_count() {
+    const char* envs[] = {nullptr, "0", "-3", "1", "3", "64", "65", "abc"};
+    const long env_val[] = {0, 0, -3, 1, 3, 64, 65, 0};   // what each asks for (0: nothing)
+    const int ndevs[] = {0, 1, 2, 8};
+    const size_t counts[] = {1, 2, 70};
+    u64 overrides = 0, ignored = 0;
+    for (int ndev : ndevs)
+        for (int num_gpus : {-1, 0, 1, 2, ndev, ndev + 1})
+            for (size_t e = 0; e < 8; e++)
+                for (size_t count : counts) {
+                    int ng = -7;
+                    std::string err = "untouched";
+                    const int rc = bp::resolve_host_shards(num_gpus, ndev, envs[e], count, &ng, &err);
+                    if (ndev == 0) {
+                        CHECK(rc == 2 && err == "no HIP device" && ng == -7, "ndev = 0: rc %d '%s'", rc, err.c_str());
+                        continue;
+                    }
+                    if (num_gpus > ndev) {
+                        char want[96];
+                        std::snprintf(want, sizeof want, "num_gpus = %d but %d HIP device(s) visible", num_gpus, ndev);
+                        CHECK(rc == 1 && err == want && ng == -7, "num_gpus %d ndev %d: rc %d '%s'", num_gpus, ndev, rc, err.c_str());
+                        continue;
+                    }
+                    long want = num_gpus >= 1 ? num_gpus : ndev;
+                    if (num_gpus < 1 && env_val[e] >= 1) {
+                        want = env_val[e] > 64 ? 64 : env_val[e];
+                        if ((size_t)want > count) want = (long)count;
+                        overrides++;
+                    }
+                    if (num_gpus >= 1 && env_val[e] >= 1 && env_val[e] != num_gpus) ignored++;
+                    CHECK(rc == 0 && ng == want, "num_gpus %d ndev %d env %s count %zu: rc %d ng %d, want %ld", num_gpus, ndev,
+                          envs[e] ? envs[e] : "(null)", count, rc, ng, want);
+                    CHECK(err == "untouched", "a message without an error");
+                }
+    CHECK(overrides > 0 && ignored > 0, "the grid never reached the override / never had one to ignore");
+}
+
+// ------------------------------------------------------------------ fan-out
+static std::vector<bp::HostShard> unit_shards(int ns) { return bp::plan_host_shards((size_t)ns, ns); }   // d = 0 .. ns - 1
+
+// a shard's wait for the flag (bounded: a flag that is never raised fails the check, it does not hang it)
+static bool wait_raised(const bp::HostStop& stop) {
+    const auto until = std::chrono::steady_clock::now() + std::chrono::seconds(60);
+    while (!stop.raised() && std::chrono::steady_clock::now() < until) std::this_thread::yield();
+    return stop.raised();
+}
+
+static void fanout() {
+    const std::thread::id me = std::this_thread::get_id();
+    // every shard succeeds: each callback once, on the caller's thread only for one shard with d = 0
+    std::vector<std::vector<bp::HostShard>> plans;
+    for (int ns : {1, 2, 3, 8}) plans.push_back(unit_shards(ns));
+    plans.push_back({bp::HostShard{2, 0, 5}});   // one shard, not the caller's device
+    for (const auto& shards : plans) {
+        const size_t ns = shards.size();
+        std::vector<std::atomic<int>> ran(64);
+        std::vector<std::thread::id> tid(64);
+        std::atomic<size_t> exits(0);
+        const bp::HostFanFailure f = bp::host_fanout(shards, [&](const bp::HostShard& sh, const bp::HostStop& stop, std::string&) {
+            ran[sh.d]++;
+            tid[sh.d] = std::this_thread::get_id();
+            const int rc = stop.raised() ? 9 : 0;
+            exits++;
+            return rc;
+        });
+        CHECK(f.k == ns && f.rc == 0 && f.err.empty(), "success reported as a failure of shard %zu", f.k);
+        CHECK(exits == ns, "%zu of %zu callbacks had returned", (size_t)exits, ns);
+        const bool inline_run = ns == 1 && shards[0].d == 0;
+        for (const bp::HostShard& sh : shards) {
+            CHECK(ran[sh.d] == 1, "shard %d ran %d times", sh.d, (int)ran[sh.d]);
+            CHECK((tid[sh.d] == me) == inline_run, "shard %d of %zu on the wrong thread", sh.d, ns);
+        }
+    }
+    // shard k fails, the others succeed
+    for (int ns : {1, 2, 3, 8})
+        for (int k = 0; k < ns; k++) {
+            std::atomic<int> exits(0);
+            const bp::HostFanFailure f =
+                bp::host_fanout(unit_shards(ns), [&](const bp::HostShard& sh, const bp::HostStop&, std::string& err) {
+                    err = "shard " + std::to_string(sh.d) + (sh.d == k ? " failed" : " left a stale message");
+                    exits++;
+                    return sh.d == k ? 40 + k : 0;
+                });
+            CHECK(f.k == (size_t)k && f.rc == 40 + k && f.err == "shard " + std::to_string(k) + " failed",
+                  "ns %d, shard %d failing: reported %zu rc %d '%s'", ns, k, f.k, f.rc, f.err.c_str());
+            CHECK(exits == ns, "%d of %d callbacks had returned", (int)exits, ns);
+        }
+    // shards 1 and 3 of 5 fail on their own, one at once and the other only after the flag is up; 2 and
+    // 4 (and 0, or not) stop for the flag: shard 1 is reported, whichever failed first
+    for (int first : {1, 3})
+        for (bool zero_stops : {false, true}) {
+            std::atomic<int> exits(0), stopped(0);
+            const bp::HostFanFailure f =
+                bp::host_fanout(unit_shards(5), [&](const bp::HostShard& sh, const bp::HostStop& stop, std::string& err) {
+                    int rc = 0;
+                    if (sh.d == 1 || sh.d == 3) {
+                        rc = sh.d != first && !wait_raised(stop) ? 99 : 50 + sh.d;
+                        err = "own " + std::to_string(sh.d);
+                    } else if (sh.d != 0 || zero_stops) {
+                        rc = wait_raised(stop) ? bp::HOST_SHARD_STOPPED : 99;
+                        err = "stopped";
+                        stopped++;
+                    }
+                    exits++;
+                    return rc;
+                });
+            CHECK(f.k == 1 && f.rc == 51 && f.err == "own 1", "first %d, shard 0 %s: reported %zu rc %d '%s'", first,
+                  zero_stops ? "stops" : "succeeds", f.k, f.rc, f.err.c_str());
+            CHECK(exits == 5 && stopped == (zero_stops ? 3 : 2), "%d callbacks had returned, %d stopped", (int)exits, (int)stopped);
+        }
 }
 
 // ------------------------------------------------------------------ owner
@@ -189,6 +310,8 @@ static void owner_case(size_t Lr, bool with_attempts, long fail_at) {
 
 int main() {
     plan();
+    shard_count();
+    fanout();
     for (size_t Lr : {size_t(0), size_t(4)})
         for (bool att : {false, true})
             for (long k = 0; k <= 4 * 8 + 1; k++) owner_case(Lr, att, k);

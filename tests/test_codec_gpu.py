@@ -206,6 +206,27 @@ def test_argument_errors(bp, cases, golden):
         bp.batch_range_proof_verify_bytes_host(blobs[0], n, *gens, check=3)
 
 
+def test_verify_bytes_too_many_gpus(bp, oracle):
+    """num_gpus beyond the visible devices: the code and message of every host-data entry point
+    (tests/test_commit_gpu.py asserts the same of the commitments), a sentinel-filled ok untouched."""
+    import ctypes
+
+    from cudabulletproof_amd import synth
+    blob = np.frombuffer(cr.encode(oracle, synth.proofs(3, 8, seed=3), 8, False), np.uint8).copy()
+    G, H = (np.ascontiguousarray(oracle.base_points(8, k), np.uint64) for k in (1, 2))
+    g, h = (np.ascontiguousarray(x, np.uint64) for x in oracle.gh())
+    L = bp.lib()
+    ndev = bp.require_gpu()
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)
+    gv, hv = bp.PointVector(p(G).value, 8), bp.PointVector(p(H).value, 8)
+    ok = np.full(3, 0xA5, np.uint8)
+    rc = L.hipbp_batch_range_proof_verify_bytes_host(p(blob), ctypes.c_size_t(len(blob)), None, ctypes.c_size_t(8),
+                                                     ctypes.byref(gv), ctypes.byref(hv), p(g), p(h), ctypes.c_int(1),
+                                                     ctypes.c_int(ndev + 1), p(ok))
+    assert rc == 1 and L.hipbp_last_error().decode() == f"num_gpus = {ndev + 1} but {ndev} HIP device(s) visible"
+    assert (ok == 0xA5).all()
+
+
 def test_release_stream_workspaces_then_encode(bp, cases):
     import torch
     n, arrs, blobs = cases["tiled600"]

@@ -37,8 +37,8 @@ def _run(exe):
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     checks, fails = (int(x) for x in r.stdout.split("\n")[-2].split())
     # 270 plans of at least 4 checks and, at count = 65537 and chunk = 1, 3 per chunk (15 plans of 65537
-    # chunks); 136 owner cases of at least 6
-    assert fails == 0 and checks >= 270 * 4 + 15 * 65537 * 3 + 136 * 6, r.stdout[-3000:]
+    # chunks); 136 owner cases of at least 6; 937 checks of the shard count and 76 of the fan-out
+    assert fails == 0 and checks >= 270 * 4 + 15 * 65537 * 3 + 136 * 6 + 937 + 76, r.stdout[-3000:]
     return r
 
 
