@@ -85,9 +85,11 @@ def generators(src, n):
     return src.base_points(n, 1), src.base_points(n, 2), Q
 
 
-def make_case(R, case, n, recipe):
-    """One case through the reference: dict of the stored outputs."""
-    a, b, tr, c_over = case_inputs(case, n, recipe)
+def make_case(R, case, n, recipe, inputs=None, verify=True):
+    """One case through the reference: dict of the stored outputs.  inputs: (a, b, transcript,
+    c_override) in place of case_inputs' (make_ipa_prove_sizes.py's recipes); verify=False leaves
+    P, the verdicts and the check point (three more O(n) passes) zero."""
+    a, b, tr, c_over = case_inputs(case, n, recipe) if inputs is None else inputs
     G, H, Q = generators(R, n)
     c_in = po.fe()
     R.f("inner_product")(po._p(c_in), po._p(a), po._p(b), po._sz(n))
@@ -98,6 +100,9 @@ def make_case(R, case, n, recipe):
     assert pr is not None and len(pr["a"]) == 1 and len(pr["L"]) == n.bit_length() - 1
     c_final = po.fe()
     R.f("inner_product")(po._p(c_final), po._p(pr["a"]), po._p(pr["b"]), po._sz(1))
+    if not verify:
+        return dict(a=pr["a"][0], b=pr["b"][0], x=pr["x"], c_in=c_in, c_final=c_final, L=pr["L"].reshape(-1, 16),
+                    R=pr["R"].reshape(-1, 16), P=po.ge(), ok_in=False, ok_final=False, check=po.ge())
     P = R.msm("msm_canon", np.concatenate([a, b]), np.concatenate([G, H]))
     ok_in = R.cuda_inner_product_verify(n, pr["a"], pr["b"], c_in, pr["L"], pr["R"], pr["x"], P, G, H, Q)
     ok_final = R.cuda_inner_product_verify(n, pr["a"], pr["b"], c_final, pr["L"], pr["R"], pr["x"], P, G, H, Q)

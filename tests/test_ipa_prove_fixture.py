@@ -1,6 +1,10 @@
 """tests/golden/ipa_prove.npz (the reference's inner_product_prove outputs, tests/golden/make_ipa_prove.py)
 is consistent with its case list and input recipes; where the reference build is available, the
-n = 8 cases are regenerated and must reproduce the stored bytes.  CPU only."""
+n = 8 cases are regenerated and must reproduce the stored bytes.  CPU only.
+
+Every input of THIS fixture has bit 255 clear (asserted below as a property of its recipes); that is
+not the prover's contract, which is the reference's bits for any limbs: ipa_prove_sizes.npz
+(test_ipa_prove_sizes_fixture.py) holds the cases with elements up to 2^256 - 1."""
 import os
 import sys
 
