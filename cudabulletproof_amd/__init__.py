@@ -25,7 +25,7 @@ LIB_PATH = os.path.join(HERE, "libcudabulletproof_hip.so")
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["bp_terms1.hip", "bp_terms2.hip", "bp_terms4.hip", "bp_terms16.hip", "bp_kernels.hip", "bp_prove.hip",
            "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_commit.hip", "bp_codec.hip", "bp_ids.hip",
-           "bp_capi.hip"]
+           "bp_api_engine.hip", "bp_api_prove.hip", "bp_api_host.hip", "bp_api_blob.hip", "bp_api_ref.hip"]
 
 _lib = None
 

@@ -1,6 +1,6 @@
 // bp_codec.h — the compact proof blob ("HBPC", version 1): its layout, its header, and
 // the per-lane bodies of the encoder and the decoder (internal to the library).  Pure like
-// bp_layout.h: no HIP runtime calls.  The kernels of bp_codec.hip and the CPU paths of bp_capi.hip
+// bp_layout.h: no HIP runtime calls.  The kernels of bp_codec.hip and the CPU paths of bp_api_blob.hip
 // call exactly the functions below, so tests/codec_check.hip runs every one of them on a CPU, the
 // malformed blobs under ASan + UBSan.
 //
@@ -115,6 +115,18 @@ struct CodecArrays {
     fe *t, *c, *x, *taux, *mu, *a, *b;
     ge *L, *R;
 };
+// ... over a batch (own_V: the proofs' own V, Vp where the batch's V is a caller's; blinding: with
+// its taux and mu, else null) and over a prover or decoder output
+inline CodecArrays codec_arrays(const hipbp_proof_batch& b, bool own_V, bool blinding) {
+    return CodecArrays{{(ge*)(own_V && b.Vp ? b.Vp : b.V), (ge*)b.A, (ge*)b.S, (ge*)b.T1, (ge*)b.T2},
+                       (fe*)b.t, (fe*)b.c, (fe*)b.x, blinding ? (fe*)b.taux : nullptr, blinding ? (fe*)b.mu : nullptr,
+                       (fe*)b.a, (fe*)b.b, (ge*)b.L, (ge*)b.R};
+}
+inline CodecArrays codec_arrays(const hipbp_proof_out& o, bool blinding) {
+    return CodecArrays{{(ge*)o.V, (ge*)o.A, (ge*)o.S, (ge*)o.T1, (ge*)o.T2},
+                       (fe*)o.t, (fe*)o.c, (fe*)o.x, blinding ? (fe*)o.taux : nullptr, blinding ? (fe*)o.mu : nullptr,
+                       (fe*)o.a, (fe*)o.b, (ge*)o.L, (ge*)o.R};
+}
 BP_DEV ge* codec_point(const CodecArrays& A, const CodecLayout& l, size_t i, size_t q) {
     if (q < 5) return A.pt[q] + i;
     q -= 5;

@@ -1,6 +1,6 @@
 // bp_ids.h — proof ids and the batch Merkle root: the hashed messages and the per-lane
 // bodies (internal to the library).  Pure like bp_codec.h: no HIP runtime calls.  The kernels of
-// bp_ids.hip and the CPU paths of bp_capi.hip call exactly the functions below, so tests/ids_check.hip
+// bp_ids.hip and the CPU paths of bp_api_blob.hip call exactly the functions below, so tests/ids_check.hip
 // runs every one of them on a CPU, the malformed blobs under ASan + UBSan.
 //
 // All integers little-endian; a proof's record is what the blob stores for it (bp_codec.h):

@@ -21,7 +21,7 @@ constexpr int TPB = 256;   // threads per block for lane-per-item kernels
 __device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
 // ------------------------------------------------------------------ tables
-// (dtab, the identity-doubling table, and two_i are built on the host: bp_capi.hip Engine::init)
+// (dtab, the identity-doubling table, and two_i are built on the host: bp_api_engine.hip Engine::init)
 // tab[b << K | p] = the first K steps of ge25519_scalarmult (curve25519_ops.cu:397-415) on base b
 // for a scalar whose top K bits are p, from the identity: one add(r, r) per bit and one add(r, P)
 // per set bit — the per-lane step of sm_lane_loop, so the same operations as the verify kernels.

@@ -134,6 +134,69 @@ struct OutLayout {
     }
 };
 
+// The prover's outputs as its kernels take them, and as the batch a verifier reads: `count` proofs of
+// n bits and Lr fold rounds, a and b of one element (Vp stays null: V is the proofs' own).
+inline ProveOut prove_out_of(const hipbp_proof_out& o) {
+    return ProveOut{(ge*)o.V, (ge*)o.A, (ge*)o.S, (ge*)o.T1, (ge*)o.T2, (fe*)o.taux, (fe*)o.mu, (fe*)o.t,
+                    (fe*)o.c, (fe*)o.x, (fe*)o.a, (fe*)o.b, (ge*)o.L, (ge*)o.R, o.valid};
+}
+inline hipbp_proof_batch batch_of(const hipbp_proof_out& o, size_t count, size_t n, size_t Lr) {
+    hipbp_proof_batch b{};
+    b.count = count; b.n = n; b.ab_len = 1; b.L_len = Lr;
+    b.V = o.V; b.A = o.A; b.S = o.S; b.T1 = o.T1; b.T2 = o.T2;
+    b.t = o.t; b.a = o.a; b.b = o.b; b.c = o.c; b.x = o.x; b.L = o.L; b.R = o.R;
+    b.taux = o.taux; b.mu = o.mu;
+    return b;
+}
+
+// ------------------------------------------------------------------ generators
+// A generator set as the library's functions hand it on: G[n], H[n], g, h and, optionally, their
+// fixed-base prefix tables (launch_prefix_tables) of `bits` bits.  tab is null exactly when bits is
+// 0: with_tables is the one way to set them and keeps that, so a consumer reads either as it is.
+// g may be null where the semantics do not read it.  Packed, on the host (pack_gens) and on the
+// device (at), the 2n + 2 points lie in the tables' base order
+//   G[n] | H[n] | h | g
+// so position k of a packed buffer is base k of its tables, and a set without g is its first 2n + 1.
+inline size_t gens_bytes(size_t n, bool with_g = true) { return (2 * n + (with_g ? 2 : 1)) * GE; }
+struct GenView {
+    const ge *G = nullptr, *H = nullptr, *g = nullptr, *h = nullptr;
+    const ge* tab = nullptr;
+    int bits = 0;
+    size_t n = 0;   // 0: loose bases (no G, H, or a caller that brings n itself)
+    GenView() = default;
+    GenView(const void* G_, const void* H_, const void* g_, const void* h_, size_t n_ = 0)
+        : G((const ge*)G_), H((const ge*)H_), g((const ge*)g_), h((const ge*)h_), n(n_) {}
+    static GenView at(const void* base, size_t n, bool with_g = true) {
+        const uint8_t* q = (const uint8_t*)base;
+        return GenView(q, q + n * GE, with_g ? q + (2 * n + 1) * GE : nullptr, q + 2 * n * GE, n);
+    }
+    GenView with_tables(const void* t, int k) const {
+        GenView v = *this;
+        const bool on = t && k > 0;
+        v.tab = on ? (const ge*)t : nullptr;
+        v.bits = on ? k : 0;
+        return v;
+    }
+    GenView without_g() const {
+        GenView v = *this;
+        v.g = nullptr;
+        return v;
+    }
+};
+// the packed order from four host arrays (g null: its slot is left as it is) ...
+inline void pack_gens(void* dst, const void* G, const void* H, const void* g, const void* h, size_t n) {
+    uint8_t* q = (uint8_t*)dst;
+    memcpy(q, G, n * GE);
+    memcpy(q + n * GE, H, n * GE);
+    memcpy(q + 2 * n * GE, h, GE);
+    if (g) memcpy(q + (2 * n + 1) * GE, g, GE);
+}
+// ... and whether a packed G | H | h holds exactly these bytes
+inline bool packed_gens_equal(const void* packed, const void* G, const void* H, const void* h, size_t n) {
+    const uint8_t* q = (const uint8_t*)packed;
+    return memcmp(q, G, n * GE) == 0 && memcmp(q + n * GE, H, n * GE) == 0 && memcmp(q + 2 * n * GE, h, GE) == 0;
+}
+
 // ------------------------------------------------------------------ workspace tables
 // One line per device buffer: X(id, field, type, bytes) — the engine's buffer `id` backs `field`, a
 // type*, of the workspace struct the kernels take, and holds `bytes` bytes.  The engine keeps one

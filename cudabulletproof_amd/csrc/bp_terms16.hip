@@ -6,7 +6,7 @@
 
 namespace bp {
 
-// The engine's table upload (bp_capi.hip Engine::upload): the kernel reads the pinned host staging
+// The engine's table upload (bp_api_engine.hip Engine::upload): the kernel reads the pinned host staging
 // buffer directly, so the first call's path issues no copy-engine transfer (a first hipMemcpyAsync of
 // the 33-KB identity-doubling table cost ~7 ms; profiles/dropin_first_call_r05g.txt).  It lives in
 // the row-form tick's code object, which a one-proof call loads anyway.

@@ -56,7 +56,7 @@ int main() {
         for (long long env : {0ll, 1ll, 64ll, 100ll, 1ll << 21}) {
             const size_t ch = commit_chunk(count, env);
             size_t next = 0, n = 0;
-            for (size_t c0 = 0; c0 < count && n < 200; c0 += ch, n++) {   // bp_capi.hip's loop
+            for (size_t c0 = 0; c0 < count && n < 200; c0 += ch, n++) {   // commit_run's loop (bp_api_prove.hip)
                 const size_t c = count - c0 < ch ? count - c0 : ch;
                 CHECK(c0 == next && c >= 1 && c <= ch, "chunk at %zu of %zu", c0, count);
                 next = c0 + c;

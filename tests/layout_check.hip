@@ -9,6 +9,7 @@
 //   unpack:    a pattern written through the hipbp_proof_out view, unpacked into RangeProof structs
 //   tables:    every workspace buffer's bytes
 //   pippenger: the Pippenger part's shape and buffer bytes over a grid of shapes
+//   gen_view:  the generator view: pack_gens / GenView::at round trips, the packed order, the table rule
 // Prints "<checks> <failures>"; exit status 1 on any failure.
 #include <cstdio>
 #include <cstdlib>
@@ -396,7 +397,56 @@ static void pippenger() {
     CHECK(seen_odd && seen_sparse && seen_nbq1, "pip grid: n %% 4 != 0, n < 2^c / 4, N / BID_PIECE == 0");
 }
 
+// The generator view and its packed order: for n = 1, 2, 4 pack_gens followed by GenView::at gives the
+// four inputs back; position k of the packed buffer is base k of the prefix-table order (G[0..n),
+// H[0..n), h, g: launch_prefix_tables' bases, row 2n h's and row 2n + 1 g's); a view without g is the
+// first 2n + 1 points; tab is null exactly when bits is 0.
+static void gen_view() {
+    for (size_t n : {(size_t)1, (size_t)2, (size_t)4}) {
+        std::vector<ge25519> G(n), H(n);
+        ge25519 g, h;
+        fill(G.data(), n * 128); fill(H.data(), n * 128); fill(&g, 128); fill(&h, 128);
+        CHECK(bp::gens_bytes(n) == (2 * n + 2) * 128 && bp::gens_bytes(n, false) == (2 * n + 1) * 128, "gens_bytes n=%zu", n);
+        std::vector<ge25519> buf(2 * n + 2);   // exactly the packed set: an overrun is the sanitizer's
+        bp::pack_gens(buf.data(), G.data(), H.data(), &g, &h, n);
+        const bp::GenView v = bp::GenView::at(buf.data(), n);
+        CHECK(v.n == n && v.tab == nullptr && v.bits == 0, "view header n=%zu", n);
+        const ge25519 *vG = (const ge25519*)v.G, *vH = (const ge25519*)v.H;
+        for (size_t i = 0; i < n; i++) CHECK(same(vG[i], G[i]) && same(vH[i], H[i]), "G, H [%zu] n=%zu", i, n);
+        CHECK(same(*(const ge25519*)v.g, g) && same(*(const ge25519*)v.h, h), "g, h n=%zu", n);
+        // the table base order, by position
+        for (size_t k = 0; k < 2 * n + 2; k++) {
+            const ge25519& want = k < n ? G[k] : k < 2 * n ? H[k - n] : k == 2 * n ? h : g;
+            CHECK(same(buf[k], want), "packed position %zu n=%zu", k, n);
+        }
+        CHECK((const void*)v.G == &buf[0] && (const void*)v.H == &buf[n] && (const void*)v.h == &buf[2 * n] &&
+              (const void*)v.g == &buf[2 * n + 1], "view pointers n=%zu", n);
+        CHECK(bp::packed_gens_equal(buf.data(), G.data(), H.data(), &h, n), "packed_gens_equal on its own bytes");
+        ge25519 h2 = h;
+        ((uint8_t*)&h2)[127] ^= 1;
+        CHECK(!bp::packed_gens_equal(buf.data(), G.data(), H.data(), &h2, n), "packed_gens_equal sees h's last byte");
+        // without g: 2n + 1 points, g's slot untouched, the view's g null
+        std::vector<ge25519> buf1(2 * n + 1);
+        bp::pack_gens(buf1.data(), G.data(), H.data(), nullptr, &h, n);
+        CHECK(memcmp(buf1.data(), buf.data(), (2 * n + 1) * 128) == 0, "pack without g n=%zu", n);
+        const bp::GenView v1 = bp::GenView::at(buf1.data(), n, false);
+        CHECK(v1.g == nullptr && (const void*)v1.h == &buf1[2 * n] && v1.without_g().g == nullptr && v.without_g().g == nullptr &&
+              v.without_g().h == v.h, "view without g n=%zu", n);
+        // tables: null exactly when bits == 0, whatever is passed
+        const bp::ge* t = (const bp::ge*)buf.data();
+        const bp::GenView w4 = v.with_tables(t, 4), w0 = v.with_tables(t, 0), wn = v.with_tables(nullptr, 4);
+        CHECK(w4.tab == t && w4.bits == 4 && w4.G == v.G && w4.g == v.g && w4.n == n, "with_tables(t, 4)");
+        CHECK(w0.tab == nullptr && w0.bits == 0, "bits == 0 must give a null table");
+        CHECK(wn.tab == nullptr && wn.bits == 0, "a null table must give bits == 0");
+        CHECK(w4.with_tables(nullptr, 0).tab == nullptr && w4.with_tables(nullptr, 0).bits == 0, "tables taken off");
+        const bp::GenView loose(G.data(), H.data(), &g, &h);   // four loose pointers: no tables, no n
+        CHECK((const void*)loose.G == G.data() && (const void*)loose.H == H.data() && (const void*)loose.g == &g &&
+              (const void*)loose.h == &h && loose.tab == nullptr && loose.bits == 0 && loose.n == 0, "loose view");
+    }
+}
+
 int main() {
+    gen_view();
     offsets();
     pack_view();
     unpack();

@@ -13,6 +13,9 @@ stand-alone host program:
   field of pip_shape and every buffer's bytes equal the expressions bp_pippenger.hip computed in line
   before it had a table; the grid reaches both key widths, a part with and without the LDS tail,
   n % 4 != 0, n < 2^c / 4 and a bidfill queue of one entry.
+* the generator view: for n in {1, 2, 4} pack_gens followed by GenView::at gives back G, H, g and h,
+  position k of the packed buffer is base k of the prefix-table order (G | H | h | g), a set without
+  g is its first 2n + 1 points, and a view's table is null exactly when its bits are 0.
 
 Once at -O2 and once under AddressSanitizer + UndefinedBehaviourSanitizer (host code only, nothing
 loaded into Python): the round trips use exactly sized buffers and free every vector handed out."""

@@ -243,6 +243,31 @@ def test_n64_both_checks(bp, T, oracle, gens_for, rs, check):
     accepted_equals_explicit(bp, T, n, vd, gd, G, H, g, h, o)
 
 
+@pytest.mark.parametrize("bits", [0, 4])
+@pytest.mark.parametrize("check", [1, 2])
+def test_gens_matches_plain_both_checks(bp, T, gens_for, check, bits):
+    """The accepted prover on a Generators set == the plain call on the same four generators, bit for
+    bit: every output tensor and attempts, under check 1 and check 2, without tables and with 4-bit
+    ones (the check-1 verify then takes them too).  n = 4, 3 proofs: the smallest shape with L, R
+    rounds and with tables; a set whose g and h were swapped on the way gives other proofs.  The three
+    values are 0, the one value validate_range_input admits at n = 4 (for n % 8 != 7 it wants byte
+    n / 8 of the value and every byte above it zero); the proofs differ by their gamma and index."""
+    import torch
+    n, B = 4, 3
+    v, gamma = inputs(B, n, np.random.default_rng(41))
+    v[:] = 0
+    G, H, g, h = (T(x) for x in gens_for(n))
+    vd, gd = T(v), T(gamma)
+    plain = bp.batch_generate_range_proof_accepted(n, vd, gd, SEED, G, H, g, h, index_base=IB, check=check)
+    gens = bp.Generators(n, G, H, g, h, prefix_bits=bits)
+    got = bp.batch_generate_range_proof_accepted(n, vd, gd, SEED, G, H, g, h, index_base=IB, check=check, gens=gens)
+    torch.cuda.synchronize()
+    assert plain["valid"].cpu().numpy().all()   # (proofs were made: no value of the batch is refused)
+    assert torch.equal(got["attempts"], plain["attempts"])
+    same(got, plain)
+    gens.close()
+
+
 def test_argument_errors_write_nothing(bp, T, gens_for):
     """max_attempts 0 and 17, check 3, a non-NULL sL and a null attempts give HIPBP_ERR_ARG and write
     nothing; count = 0 returns HIPBP_OK."""
