@@ -247,6 +247,21 @@ int Pipeline::push(const hipbp_proof_batch* b, const ge25519* P_in, uint8_t* ok,
         if (rc != HIPBP_OK) return rc;
         if ((int)b->n != n) { g_err = "batch n differs from the pipeline's"; return HIPBP_ERR_ARG; }
         if (ring[head].active) { g_err = "pipeline slot busy (internal)"; return HIPBP_ERR_ARG; }
+        // admission before anything is staged: a refused push leaves the pipeline as it was
+        const int defer = (defer_msm && bp::batch_defers(cfg, (int)b->L_len)) ? 1 : 0;
+        const bp::PlanError adm = bp::push_admits(cfg, ring, D, head, b->count, (int)b->L_len, defer);
+        if (adm != bp::PLAN_OK && !busy()) {
+            g_err = "pipeline tick exceeds 2^32 lanes (batch too large for n)";
+            return HIPBP_ERR_ARG;
+        }
+        if (adm != bp::PLAN_OK) {
+            g_err = adm == bp::PLAN_OVERFLOW
+                        ? "push refused: with the batches in flight a tick would exceed the region list; run a drain "
+                          "tick (push(NULL)) and retry"
+                        : "push refused: with the batches in flight a tick would exceed 2^32 lanes; run a drain tick "
+                          "(push(NULL)) and retry";
+            return HIPBP_ERR_ARG;
+        }
         BP_RET_ON(carve(nw, b->count, b->L_len));
         nw.dev.bv = view_of(b);
         nw.dev.ok = ok;
@@ -258,7 +273,7 @@ int Pipeline::push(const hipbp_proof_batch* b, const ge25519* P_in, uint8_t* ok,
         nw.dev.lane_tree = cfg.lane_tree ? 1 : 0;
         nw.dev.ptab = pbits ? tables() : nullptr;
         nw.dev.pbits = pbits;
-        nw.dev.defer = (defer_msm && bp::batch_defers(cfg, (int)b->L_len)) ? 1 : 0;
+        nw.dev.defer = defer;
         BP_RET_ON(plan_sort(nw, head));
         BP_RET_ON(hipEventSynchronize(nw.copied));   // staging slot free again
         host_dev[head] = nw.dev;

@@ -170,6 +170,44 @@ inline void advance_ring(const PlanConfig& c, PlanSlot* slots, int D, int& head)
     head = (head + 1) % D;
 }
 
+// ------------------------------------------------------------------ admission
+// May a batch (B, L, defer) be staged in slot `head`?  PLAN_OK: yes, and then every tick the ring
+// still needs plans, whatever is admitted after it (each later batch passes this test itself).
+// Otherwise the error the ring would run into with the batch in it; the caller stages nothing.
+// Batches of different round counts can reach their two-region stages in one tick (round counts
+// descending by one per push all run RK_FINAL_TERMS together), which the region list cannot always
+// hold, so the ring is played forward on a copy, the candidate included, until it is idle: the
+// ticks of a drain, and further pushes are tested against what is then in flight.  An idle ring
+// admits every batch that plans at all, so a refused batch is admitted after at most D drain ticks.
+// A ring whose batches all share the candidate's (L, defer) has at most one batch per stage: L + 6
+// regions, 2 L + 5 when split (defer_ok), both within MAX_REGIONS; and a batch's items of all its
+// stages together are below B (8 n + 24) (RK_TREE 2 n B, stage 0 (4 n + 9) B, the rounds 2 n B, the
+// one-per-proof regions 9 B), 16 lanes each at the most, with the regions' alignment far below 2^20
+// lanes: such a ring needs no replay (the steady state's push scans its D slots and no more).
+inline PlanError push_admits(const PlanConfig& c, const PlanSlot* slots, int D, int head, unsigned long long B,
+                             int L, int defer) {
+    bool uniform = true;
+    unsigned long long sumB = B;
+    for (int k = 0; k < D; k++)
+        if (slots[k].active) {
+            uniform &= slots[k].L == L && slots[k].defer == defer;
+            sumB += slots[k].B;
+        }
+    if (uniform && sumB < ((1ull << 32) - (1ull << 20)) / (16ull * (8ull * c.n + 24))) return PLAN_OK;
+    PlanSlot sim[MAX_DEPTH];
+    for (int k = 0; k < D; k++) sim[k] = slots[k];
+    sim[head] = PlanSlot{true, 0, B, L, defer};
+    for (bool busy = true; busy;) {
+        TickPlan t;
+        const PlanError pe = plan_tick(c, sim, D, head, t);
+        if (pe != PLAN_OK) return pe;
+        advance_ring(c, sim, D, head);
+        busy = false;
+        for (int k = 0; k < D; k++) busy |= sim[k].active;
+    }
+    return PLAN_OK;
+}
+
 // ------------------------------------------------------------------ the lane sort's sets
 // A batch's per-lane item sets in perm order (stage 0's per-lane classes, the rounds whose scalar
 // runs are shorter than a wave, the final terms), for batches of at least LANE_SORT_MIN proofs

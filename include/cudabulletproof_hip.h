@@ -188,6 +188,13 @@ int hipbp_batch_inner_product_verify(const hipbp_proof_batch* batch, const ge255
  * Returns NULL on error (see hipbp_last_error). */
 void* hipbp_pipeline_create(size_t max_batch, size_t n, int range_mode, const ge25519* G, const ge25519* H,
                             const ge25519* g, const ge25519* h, void* stream);
+/* A push is accepted or refused, never half done.  Batches of different L_len (or with and without
+ * a split stage 0) may share the ring; a batch that, with those in flight, would bring a later tick
+ * past the kernel's region list (or past 2^32 lanes) is refused: HIPBP_ERR_ARG, hipbp_last_error says
+ * "push refused ... run a drain tick (push(NULL)) and retry", no tick runs and the pipeline is exactly
+ * as before the call.  The in-flight batches complete under drain ticks or a flush as usual, and the
+ * same batch is accepted after at most `depth` drain ticks.  Batches that all have one L_len and one
+ * split setting (the steady state) are never refused for the region list. */
 int hipbp_pipeline_push(void* pipeline, const hipbp_proof_batch* batch /* NULL = drain tick */,
                         const ge25519* P_in, uint8_t* ok, ge25519* P_out, ge25519* check_out,
                         uint8_t* flags_out /* range_mode 2, nullable */, ge25519* poly_out /* idem */);
