@@ -25,6 +25,7 @@ LIB_PATH = os.path.join(HERE, "libcudabulletproof_hip.so")
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["bp_terms1.hip", "bp_terms2.hip", "bp_terms4.hip", "bp_terms16.hip", "bp_kernels.hip", "bp_prove.hip",
            "bp_prove_seed.hip", "bp_ipa_prove.hip", "bp_pippenger.hip", "bp_commit.hip", "bp_codec.hip", "bp_ids.hip",
+           "bp_gens_derive.hip",
            "bp_api_engine.hip", "bp_api_prove.hip", "bp_api_host.hip", "bp_api_blob.hip", "bp_api_ref.hip"]
 
 _lib = None
@@ -144,6 +145,8 @@ EXPORTS = [
     "hipbp_batch_range_proof_verify_bytes_host",
     "hipbp_batch_proof_ids", "hipbp_blob_proof_ids", "hipbp_merkle_root", "hipbp_proof_ids_host",
     "hipbp_blob_proof_ids_host", "hipbp_merkle_root_host", "hipbp_merkle_path_host", "hipbp_merkle_verify_host",
+    "hipbp_derive_base_points", "hipbp_derive_single_point", "hipbp_derive_base_points_host",
+    "hipbp_derive_single_point_host", "hipbp_gens_create_seeded", "hipbp_gens_copy_points",
 ]
 
 
@@ -184,9 +187,11 @@ def lib():
                   "hipbp_proofs_decode_host", "hipbp_batch_range_proof_verify_bytes_host",
                   "hipbp_batch_proof_ids", "hipbp_blob_proof_ids", "hipbp_merkle_root", "hipbp_proof_ids_host",
                   "hipbp_blob_proof_ids_host", "hipbp_merkle_root_host", "hipbp_merkle_path_host",
-                  "hipbp_merkle_verify_host"):
+                  "hipbp_merkle_verify_host", "hipbp_derive_base_points", "hipbp_derive_single_point",
+                  "hipbp_derive_base_points_host", "hipbp_derive_single_point_host", "hipbp_gens_copy_points"):
             getattr(L, f).restype = ctypes.c_int
         L.hipbp_proof_blob_bound.restype = ctypes.c_size_t
+        L.hipbp_gens_create_seeded.restype = ctypes.c_void_p
         _lib = L
     return _lib
 
@@ -466,6 +471,35 @@ class Generators:
         if not self.h:
             raise BulletproofError(L.hipbp_last_error().decode())
 
+    @classmethod
+    def from_seeds(cls, n, seed_G=None, seed_H=None, seed_g=None, seed_h=None, prefix_bits=0, stream=None):
+        """hipbp_gens_create_seeded: the set whose G, H are derive_base_points(seed_G / seed_H, n) and
+        whose g, h are derive_single_point(seed_g / seed_h), derived in place on the GPU.
+        The defaults are REFERENCE_SEEDS, the reference test driver's generators.  points() hands the
+        arrays out for the entry points that take them."""
+        L = lib()
+        seeds = [_gen_seed(REFERENCE_SEEDS[k] if s is None else s)
+                 for k, s in zip(("G", "H", "g", "h"), (seed_G, seed_H, seed_g, seed_h))]
+        self = cls.__new__(cls)
+        self.n, self.bits = int(n), int(prefix_bits)
+        self.h = L.hipbp_gens_create_seeded(_sz(n), *seeds, ctypes.c_int(self.bits), _stream_ptr(stream))
+        if not self.h:
+            raise BulletproofError(L.hipbp_last_error().decode())
+        return self
+
+    def points(self, stream=None):
+        """hipbp_gens_copy_points: (G (n,16), H (n,16), g (16,), h (16,)) as new int64 CUDA tensors on
+        the current device, copies of the set's snapshot.  Asynchronous on `stream`."""
+        import contextlib
+
+        import torch
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            z = lambda *shape: torch.empty(*shape, dtype=torch.int64, device="cuda")
+            G, H, g, h = z(self.n, 16), z(self.n, 16), z(16), z(16)
+        _chk(lib().hipbp_gens_copy_points(_c(self.h), _c(G.data_ptr()), _c(H.data_ptr()), _c(g.data_ptr()),
+                                          _c(h.data_ptr()), None, None, _stream_ptr(stream)))
+        return G, H, g, h
+
     def nbytes_tables(self):
         return (2 * self.n + 2) * (1 << self.bits) * 128 if self.bits else 0
 
@@ -576,6 +610,73 @@ def batch_generate_range_proof_seeded(n, v, gamma, seed, G, H, g, h, index_base=
                                                            _c(g.data_ptr()), _c(h.data_ptr()), ctypes.byref(oc),
                                                            _stream_ptr(stream)))
     out["_keep"] = ins
+    return out
+
+
+# ---------------------------------------------------------------------- generators from seeds
+# the reference test driver's seeds (complete_bulletproof_test.cu:66-109): byte k, then 31 zeros
+REFERENCE_SEEDS = {k: bytes([b]) + bytes(31) for k, b in (("G", 1), ("H", 2), ("g", 3), ("h", 4))}
+
+
+def _gen_seed(seed):
+    """A generator seed for the C ABI: 32 bytes, or an int 0..255 for that byte followed by 31 zeros
+    (None stays None: the C ABI's null seed)."""
+    if seed is None:
+        return None
+    if isinstance(seed, (int, np.integer)):
+        if not 0 <= int(seed) <= 255:
+            raise ValueError(f"an int seed must be 0..255, got {seed}")
+        seed = bytes([int(seed)]) + bytes(31)
+    return _seed_arg(seed)
+
+
+def derive_base_points(seed, count, first=0, out=None, stream=None):
+    """hipbp_derive_base_points: points first .. first + count - 1 of the seed's generator
+    vector, derived on the GPU: X = SHA-256(seed | BE32(i)), Y = SHA-256(X's bytes), Z = 1, T = X * Y
+    in the reference's arithmetic, the reference test driver's rule bit for bit.  first + count <= 2^32.
+    out: a contiguous (count,16) int64 CUDA tensor to write, or None for a new one on the current
+    device.  Asynchronous on `stream`.  Returns the (count,16) tensor."""
+    import contextlib
+
+    import torch
+    count = int(count)
+    if out is None:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            out = torch.empty(count, 16, dtype=torch.int64, device="cuda")
+    elif out.dtype != torch.int64 or tuple(out.shape) != (count, 16) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous ({count}, 16) int64 tensor")
+    sd = _gen_seed(seed)
+    if count:   # (an empty tensor has no address to pass)
+        _chk(lib().hipbp_derive_base_points(_c(out.data_ptr()), sd, ctypes.c_uint64(int(first)), _sz(count),
+                                            _stream_ptr(stream)))
+    return out
+
+
+def derive_single_point(seed, stream=None):
+    """hipbp_derive_single_point: the seed's single generator (the reference driver's g, h rule):
+    X = SHA-256(seed), Y = Z = 1, T = X * 1 in the reference's arithmetic.  Returns a (16,) int64 CUDA
+    tensor on the current device.  Asynchronous on `stream`."""
+    import contextlib
+
+    import torch
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        out = torch.empty(16, dtype=torch.int64, device="cuda")
+    _chk(lib().hipbp_derive_single_point(_c(out.data_ptr()), _gen_seed(seed), _stream_ptr(stream)))
+    return out
+
+
+def derive_base_points_host(seed, count, first=0):
+    """hipbp_derive_base_points_host: derive_base_points on the CPU; a (count,16) uint64 array with the
+    device call's bytes.  Needs no GPU."""
+    out = np.zeros((int(count), 16), np.uint64)
+    _chk(lib().hipbp_derive_base_points_host(_p(out), _gen_seed(seed), ctypes.c_uint64(int(first)), _sz(int(count))))
+    return out
+
+
+def derive_single_point_host(seed):
+    """hipbp_derive_single_point_host: derive_single_point on the CPU; a (16,) uint64 array.  Needs no GPU."""
+    out = np.zeros(16, np.uint64)
+    _chk(lib().hipbp_derive_single_point_host(_p(out), _gen_seed(seed)))
     return out
 
 

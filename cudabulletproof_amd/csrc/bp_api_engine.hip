@@ -3,7 +3,8 @@
 // device data that neither prove nor encode:
 //   hipbp_last_error, hipbp_device_count, hipbp_sync, hipbp_timing_enable / _collect,
 //   hipbp_kernel_count / _name, hipbp_release_stream_workspaces
-//   hipbp_gens_create / _destroy
+//   hipbp_gens_create / _create_seeded / _copy_points / _destroy
+//   hipbp_derive_base_points / _single_point, and their _host forms (CPU only: no HIP call)
 //   hipbp_batch_range_proof_verify / _std / _gens, hipbp_batch_inner_product_verify
 //   hipbp_pipeline_create / _push / _flush / _prefix_tables / _depth / _destroy / _use_gens / _defer_msm
 //   hipbp_msm / _batch / _batch_gens, hipbp_msm_pippenger / _batch / _windows / _horner
@@ -12,6 +13,7 @@
 // hipbp_last_error.  Unlike the reference, no call allocates and frees device memory of its own: a
 // per-device engine keeps grow-only buffers, the identity-doubling and 2^i tables, and one stream.
 #include "bp_engine.h"
+#include "bp_gens_derive.h"
 
 namespace bpe __attribute__((visibility("hidden"))) {
 
@@ -386,6 +388,50 @@ int run_verify(Engine& e, const hipbp_proof_batch* batch, const ge25519* P_in, c
     return rc;
 }
 
+// What hipbp_gens_create and hipbp_gens_create_seeded share: the checks (sources_ok: the caller's own
+// pointers are all there), the set and its snapshot buffer, the prefix tables, the sync and the failure
+// path.  fill(d, s) enqueues on s whatever writes the 2n + 2 points at d, in place; its error is
+// reported under fill_what.
+template <class Fill>
+void* gens_build(size_t n, bool sources_ok, int prefix_bits, void* stream, const Fill& fill, const char* fill_what) {
+    hipError_t err;
+    Engine* e = engine_or_null(&err);
+    if (!e) { g_err = std::string("engine: ") + hipGetErrorString(err); return nullptr; }
+    if (!is_pow2(n) || n > MAX_N || !sources_ok) { g_err = "gens: bad n or null generator"; return nullptr; }
+    if (prefix_bits < 0 || prefix_bits > bp::PREFIX_MAX_BITS) { g_err = "gens: prefix bits must be 0..24"; return nullptr; }
+    Gens* gs = new Gens();
+    gs->device = e->device;
+    gs->n = n;
+    hipStream_t s = pick(stream);
+    auto fail = [&](hipError_t er, const char* what) -> void* {
+        g_err = std::string(what) + ": " + hipGetErrorString(er);
+        gs->release();
+        delete gs;
+        return nullptr;
+    };
+    if ((err = gs->gen.need(bp::gens_bytes(n))) != hipSuccess) return fail(err, "gens alloc");
+    const GenView d = GenView::at(gs->gen.p, n);   // the snapshot, in the packed order
+    if ((err = fill(d, s)) != hipSuccess) return fail(err, fill_what);
+    if (prefix_bits) {
+        if ((err = gs->tab.need(bp::gens_bytes(n) << prefix_bits)) != hipSuccess) return fail(err, "gens tables");
+        bp::launch_prefix_tables(gs->tab.as<bp::ge>(), d.G, d.H, d.h, d.g, (int)n, prefix_bits, s);
+        if ((err = hipGetLastError()) != hipSuccess) return fail(err, "gens tables");
+        gs->bits = prefix_bits;
+    }
+    if ((err = hipStreamSynchronize(s)) != hipSuccess) return fail(err, "gens sync");
+    return gs;
+}
+
+// null pointers and the index range of a derive call (bp_gens_derive.h: first + count <= 2^32)
+int derive_check(const void* out, const uint8_t* seed32, uint64_t first, size_t count) {
+    if (!out || !seed32) { g_err = "derive: null output or seed"; return HIPBP_ERR_ARG; }
+    if (first > bp::GENS_INDEX_END || count > bp::GENS_INDEX_END - first) {
+        g_err = "derive: first + count must be <= 2^32 (the index is hashed as 32 bits)";
+        return HIPBP_ERR_ARG;
+    }
+    return HIPBP_OK;
+}
+
 }  // namespace bpe
 
 using namespace bpe;
@@ -457,37 +503,71 @@ int hipbp_release_stream_workspaces(void* stream) {
 
 void* hipbp_gens_create(size_t n, const ge25519* G, const ge25519* H, const ge25519* g, const ge25519* h,
                         int prefix_bits, void* stream) {
-    hipError_t err;
-    Engine* e = engine_or_null(&err);
-    if (!e) { g_err = std::string("engine: ") + hipGetErrorString(err); return nullptr; }
-    if (!is_pow2(n) || n > MAX_N || !G || !H || !g || !h) { g_err = "gens: bad n or null generator"; return nullptr; }
-    if (prefix_bits < 0 || prefix_bits > bp::PREFIX_MAX_BITS) { g_err = "gens: prefix bits must be 0..24"; return nullptr; }
-    Gens* gs = new Gens();
-    gs->device = e->device;
-    gs->n = n;
-    hipStream_t s = pick(stream);
-    const size_t GE = bp::GE;
-    auto fail = [&](hipError_t er, const char* what) -> void* {
-        g_err = std::string(what) + ": " + hipGetErrorString(er);
-        gs->release();
-        delete gs;
-        return nullptr;
-    };
-    if ((err = gs->gen.need(bp::gens_bytes(n))) != hipSuccess) return fail(err, "gens alloc");
-    const GenView d = GenView::at(gs->gen.p, n);   // the snapshot, in the packed order
-    const void* const to[4] = {d.G, d.H, d.h, d.g};
-    const void* const from[4] = {G, H, h, g};
+    return gens_build(n, G && H && g && h, prefix_bits, stream, [&](const GenView& d, hipStream_t s) {
+        const void* const to[4] = {d.G, d.H, d.h, d.g};
+        const void* const from[4] = {G, H, h, g};
+        for (int k = 0; k < 4; k++)
+            if (hipError_t er = hipMemcpyAsync((void*)to[k], from[k], (k < 2 ? n : 1) * bp::GE, hipMemcpyDeviceToDevice, s))
+                return er;
+        return hipSuccess;
+    }, "gens copy");
+}
+
+void* hipbp_gens_create_seeded(size_t n, const uint8_t seed_G[32], const uint8_t seed_H[32], const uint8_t seed_g[32],
+                               const uint8_t seed_h[32], int prefix_bits, void* stream) {
+    return gens_build(n, seed_G && seed_H && seed_g && seed_h, prefix_bits, stream, [&](const GenView& d, hipStream_t s) {
+        bp::launch_derive_base_points((bp::ge*)d.G, bp::gens_seed_words(seed_G), 0, n, s);
+        bp::launch_derive_base_points((bp::ge*)d.H, bp::gens_seed_words(seed_H), 0, n, s);
+        bp::launch_derive_single_point((bp::ge*)d.h, bp::gens_seed_words(seed_h), s);
+        bp::launch_derive_single_point((bp::ge*)d.g, bp::gens_seed_words(seed_g), s);
+        return hipGetLastError();
+    }, "gens derive");
+}
+
+int hipbp_gens_copy_points(void* gens, ge25519* G, ge25519* H, ge25519* g, ge25519* h, size_t* n, int* prefix_bits,
+                           void* stream) {
+    const Gens* gs = (const Gens*)gens;
+    if (int rc = gens_check(gs, 0, nullptr)) return rc;
+    const GenView d = gs->view();
+    void* const to[4] = {G, H, h, g};
+    const void* const from[4] = {d.G, d.H, d.h, d.g};
     for (int k = 0; k < 4; k++)
-        if ((err = hipMemcpyAsync((void*)to[k], from[k], (k < 2 ? n : 1) * GE, hipMemcpyDeviceToDevice, s)) != hipSuccess)
-            return fail(err, "gens copy");
-    if (prefix_bits) {
-        if ((err = gs->tab.need(bp::gens_bytes(n) << prefix_bits)) != hipSuccess) return fail(err, "gens tables");
-        bp::launch_prefix_tables(gs->tab.as<bp::ge>(), d.G, d.H, d.h, d.g, (int)n, prefix_bits, s);
-        if ((err = hipGetLastError()) != hipSuccess) return fail(err, "gens tables");
-        gs->bits = prefix_bits;
+        if (to[k]) BP_RET_ON(hipMemcpyAsync(to[k], from[k], (k < 2 ? gs->n : 1) * bp::GE, hipMemcpyDeviceToDevice, pick(stream)));
+    if (n) *n = gs->n;
+    if (prefix_bits) *prefix_bits = gs->bits;
+    return HIPBP_OK;
+}
+
+int hipbp_derive_base_points(ge25519* out, const uint8_t seed32[32], uint64_t first, size_t count, void* stream) {
+    if (int rc = derive_check(out, seed32, first, count)) return rc;
+    if (count == 0) return HIPBP_OK;
+    bp::launch_derive_base_points((bp::ge*)out, bp::gens_seed_words(seed32), first, count, pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_derive_single_point(ge25519* out, const uint8_t seed32[32], void* stream) {
+    if (int rc = derive_check(out, seed32, 0, 1)) return rc;
+    bp::launch_derive_single_point((bp::ge*)out, bp::gens_seed_words(seed32), pick(stream));
+    BP_RET_ON(hipGetLastError());
+    return HIPBP_OK;
+}
+
+int hipbp_derive_base_points_host(ge25519* out, const uint8_t seed32[32], uint64_t first, size_t count) {
+    if (int rc = derive_check(out, seed32, first, count)) return rc;
+    const bp::GenSeed seed = bp::gens_seed_words(seed32);
+    for (size_t k = 0; k < count; k++) {
+        const bp::ge p = bp::derive_base_point(seed, (uint32_t)(first + k));
+        memcpy(out + k, &p, sizeof p);
     }
-    if ((err = hipStreamSynchronize(s)) != hipSuccess) return fail(err, "gens sync");
-    return gs;
+    return HIPBP_OK;
+}
+
+int hipbp_derive_single_point_host(ge25519* out, const uint8_t seed32[32]) {
+    if (int rc = derive_check(out, seed32, 0, 1)) return rc;
+    const bp::ge p = bp::derive_single_point(bp::gens_seed_words(seed32));
+    memcpy(out, &p, sizeof p);
+    return HIPBP_OK;
 }
 
 void hipbp_gens_destroy(void* gens) {

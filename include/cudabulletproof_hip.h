@@ -217,6 +217,36 @@ int hipbp_pipeline_prefix_tables(void* pipeline, int bits);
 void* hipbp_gens_create(size_t n, const ge25519* G, const ge25519* H, const ge25519* g, const ge25519* h,
                         int prefix_bits, void* stream);
 void hipbp_gens_destroy(void* gens);
+/* Generators derived from 32-byte seeds (no library counterpart in the reference: the rule is its
+ * test driver's, complete_bulletproof_test.cu:33-109, bit for bit).
+ *   vector form, point i:  X = le(SHA-256(seed32 | BE32(i)))  Y = le(SHA-256(the 32 bytes of X))
+ *                          Z = 1                              T = fe25519_mul(X, Y)
+ *   single form (g, h):    X = le(SHA-256(seed32))            Y = Z = 1    T = fe25519_mul(X, 1)
+ * le() is a plain little-endian load: bit 255 is kept and nothing is reduced or canonicalised; T is
+ * a product in the reference's arithmetic in both forms.  out[k] is point first + k.  Only the low
+ * 32 bits of an index are hashed, so first + count <= 2^32 is required; a block [first, first + count)
+ * gives the same bytes however it is cut into calls.  count = 0 returns HIPBP_OK and writes nothing;
+ * a null out or seed32, or first + count > 2^32, gives HIPBP_ERR_ARG, writes nothing and enqueues
+ * nothing.
+ * device out[count]; seed32 is HOST memory, read at the call (the caller may free it on return);
+ * asynchronous on stream */
+int hipbp_derive_base_points(ge25519* out, const uint8_t seed32[32], uint64_t first, size_t count, void* stream);
+int hipbp_derive_single_point(ge25519* out, const uint8_t seed32[32], void* stream);
+/* the same on host memory, on the CPU (one thread); works in a process that sees no device */
+int hipbp_derive_base_points_host(ge25519* out, const uint8_t seed32[32], uint64_t first, size_t count);
+int hipbp_derive_single_point_host(ge25519* out, const uint8_t seed32[32]);
+/* hipbp_gens_create with the four arrays derived in place (no staging buffer, no copy): G and H the
+ * first n points of seed_G's and seed_H's vectors, g and h the single points of seed_g and seed_h;
+ * then the prefix tables as before.  The seeds are HOST memory, read at the call.  The checks on n
+ * and prefix_bits are hipbp_gens_create's.  Synchronous; NULL on error. */
+void* hipbp_gens_create_seeded(size_t n, const uint8_t seed_G[32], const uint8_t seed_H[32],
+                               const uint8_t seed_g[32], const uint8_t seed_h[32], int prefix_bits, void* stream);
+/* Copy a set's points out to caller-owned DEVICE buffers G[n], H[n], g[1], h[1] (any may be NULL =
+ * skip); *n and *prefix_bits (HOST, nullable) are written at the call.  For the entry points that
+ * take arrays (a seeded set's caller never held its points); serves any set.  A null gens, or one
+ * created on another device, gives HIPBP_ERR_ARG.  Asynchronous on stream. */
+int hipbp_gens_copy_points(void* gens, ge25519* G, ge25519* H, ge25519* g, ge25519* h, size_t* n, int* prefix_bits,
+                           void* stream);
 /* The pipeline reads its generators and prefix tables from `gens` (same n; the pipeline must be
  * idle; the set must outlive the pipeline's use of it).  Results keep their bits. */
 int hipbp_pipeline_use_gens(void* pipeline, void* gens);
